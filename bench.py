@@ -7,13 +7,20 @@ Lucchi++ test volume (configs[1]): 165 x 1024 x 768, roi 112^3, overlap 0.5, bum
 the volume is resident in HBM before it starts).  value = window-voxels/s of the whole job (all ranks).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Reported next to `value` (rank 0): the same job with 8-flip mean TTA through InferenceManager (`tta8`), the cubic 448^3
-volume (`cube448`), the fp32 parity path (`fp32`), the training half of the metric (`train`, with its own roofline), RSUNet
-and the MONAI-style residual U-Net (configs[4]) legs, the CPU oracle on the host cores (`cpu_baseline`), and for N > 1 the
-strong-scaling slab mode (`strong_slab`: ONE volume cut into N slabs with p2p halo bands, inference/slab.py).
+A plain run does only what the headline needs: set up, `--warmup` untimed steps, `--steps` timed steps, the outputs of the last
+timed step if `--dump-outputs DIR` is given (see dump_outputs), and the JSON line (`value`, `ms_per_step` = milliseconds of one
+timed step, ...).  The secondary legs below run only with `--full` (each can still be switched off there by its --no-* option).
+
+Reported next to `value` with `--full` (rank 0): the per-kernel `roofline` (with live rocprofv3 counter passes), the same job
+with 8-flip mean TTA through InferenceManager (`tta8`), the cubic 448^3 volume (`cube448`), the fp32 parity path (`fp32`), the
+training half of the metric (`train`, with its own roofline), RSUNet and the MONAI-style residual U-Net (configs[4]) legs, the
+CPU oracle on the host cores (`cpu_baseline`), and for N > 1 the strong-scaling slab mode (`strong_slab`: ONE volume cut into N
+slabs with p2p halo bands, inference/slab.py).
 
 Multi-GPU headline: the path shards by independent volumes (the reference's volume-per-rank sharding,
 training/lightning/data.py:234-266): every rank owns one volume, no data-path collective -> weak scaling.
@@ -93,6 +100,36 @@ def job_record(n_windows, views, vol_shape, seconds, **extra):
            "output_voxels_per_s": out_vox / seconds, "volume": list(vol_shape)}
     rec.update(extra)
     return rec
+
+
+DUMP_WHOLE_BYTES = 32 << 20        # an output up to this size is written whole
+DUMP_SAMPLE = 1 << 22              # otherwise: this many seeded flat positions (16 MB in float32) ...
+DUMP_PLANE_BYTES = 16 << 20        # ... and the central z plane of channel 0 if it fits here: 48 MB at most in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out, directory):
+    """What the timed path returned in its last step, as float32 .npy files under `directory`, so that two builds can be compared
+    output for output (same arguments -> same inputs, same file names, same sample positions).  A small output is written whole
+    (`output`, its own shape); a larger one as `output_sample` -- the values at the sorted, de-duplicated flat positions
+    numpy.random.default_rng(DUMP_SEED).integers(0, numel, DUMP_SAMPLE) -- plus `output_mid_z_plane`, the whole central z plane of
+    channel 0 of a (N, C, D, H, W) output.  -> {name: shape}"""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    out = out.detach()
+    arrays = {}
+    if out.numel() * 4 <= DUMP_WHOLE_BYTES:
+        arrays["output"] = out.float().cpu().numpy()
+    else:
+        flat = out.reshape(-1)
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=DUMP_SAMPLE))
+        arrays["output_sample"] = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        if out.dim() == 5 and out.shape[3] * out.shape[4] * 4 <= DUMP_PLANE_BYTES:
+            arrays["output_mid_z_plane"] = out[0, 0, out.shape[2] // 2].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 class HeadlineWatchdog:
@@ -768,11 +805,23 @@ def live_pmc_traffic_bytes(label, timeout_s=90):
     return _traffic_from_table(live_pmc_table(timeout_s), key)
 
 
-def main():
+def parse_args(argv=None):
+    def count(lo):
+        def parse(s):
+            v = int(s)
+            if v < lo:
+                raise argparse.ArgumentTypeError(f"must be >= {lo}, got {v}")
+            return v
+        return parse
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=count(1), default=5, help="timed steps")
+    ap.add_argument("--warmup", type=count(0), default=1, help="untimed steps before them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: roofline, tta8 / cube448 / fp32 / configs[2-3], train, U-Nets, cpu_baseline, "
+                         "strong_slab")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC passes only (no rocprofv3 child runs)")
@@ -780,7 +829,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the tta8 / cube448 / fp32 / U-Net legs")
     ap.add_argument("--train-batch", type=int, default=4)
     ap.add_argument("--train-steps", type=int, default=10)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -840,7 +894,7 @@ def main():
     def step():
         return eng(vol, model)       # the product call: probe, accumulators, all window batches, finalize, crop
 
-    exc, dt, out_shape = None, float("nan"), ()
+    exc, dt, out_shape, last = None, float("nan"), (), None
     try:
         with torch.no_grad():
             for _ in range(args.warmup):
@@ -858,6 +912,8 @@ def main():
                     out = step()
             torch.cuda.synchronize()
             out_shape = tuple(out.shape)
+            if args.dump_outputs and rank == 0:
+                last = out
             del out
         except Exception as e:     # noqa: BLE001
             exc = e
@@ -878,6 +934,10 @@ def main():
         dt = float(t.item())
     per_call = dt / args.steps
     value_vps = world * n_win * ROI_VOX * args.steps / dt
+    dumped = None
+    if last is not None:          # rank 0's output: the files stay within dump_outputs' size bound whatever N is
+        dumped = {"dir": str(args.dump_outputs), "rank": 0, "arrays": dump_outputs(last, args.dump_outputs)}
+        del last
 
     def headline_fields():
         return {
@@ -896,6 +956,7 @@ def main():
             "window_voxels_per_s": value_vps,
             "output_voxels_per_s": world * volume[0] * volume[1] * volume[2] * args.steps / dt,
             "ms_per_8_windows": per_call * 1e3 * SW_BATCH / n_win, "timed_region_s": dt, "output_shape": list(out_shape),
+            "full": full, **({"dump_outputs": dumped} if dumped else {}),
         }
 
     # the secondary legs below may not cost the headline: see HeadlineWatchdog (PYTC_BENCH_WATCHDOG_S, 0 = off)
@@ -908,10 +969,10 @@ def main():
         rec["errors"] = dict(errors, watchdog={str(rank): f"secondary legs did not finish within {budget:.0f} s of the timed region; "
                                                           "headline only"})
         return json.dumps(rec)
-    watchdog = HeadlineWatchdog(budget, rescue_line).arm()
+    watchdog = HeadlineWatchdog(budget if full else 0.0, rescue_line).arm()      # a plain run has no secondary legs
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and full and not args.no_roofline:
         (wz, wy, wx), combine = eng._axis_vectors(dev)
         value = torch.zeros((1,) + tuple(max(volume[a], ROI[a]) for a in range(3)), device=dev)
         weight = torch.zeros(value.shape[1:], device=dev)
@@ -947,7 +1008,7 @@ def main():
                       f"GB/s={v['bytes'] / max(v['ms'], 1e-9) / 1e6:8.1f}", file=sys.stderr)
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and full and not args.no_extras:
         from pytorch_connectomics_amd.inference import InferenceManager
         with torch.no_grad():
             try:   # secondary figures must never cost the headline line
@@ -994,7 +1055,7 @@ def main():
     del vol
     torch.cuda.empty_cache()
     strong = None
-    if world > 1:
+    if world > 1 and full:
         from pytorch_connectomics_amd.inference.slab import slab_extent, slab_predict_volume
         exc, ds = None, float("nan")
         try:
@@ -1026,7 +1087,7 @@ def main():
         torch.cuda.empty_cache()
 
     train = None
-    if not args.no_train:
+    if full and not args.no_train:
         exc = None
         try:
             train = train_leg(dev, rank, world, args, barrier)
@@ -1036,7 +1097,7 @@ def main():
             train = None
 
     rsu = unet = None
-    if rank == 0 and world == 1 and not args.no_train and not args.no_extras:
+    if rank == 0 and world == 1 and full and not args.no_train and not args.no_extras:
         for name, leg in (("rsunet", rsunet_leg), ("monai_unet", monai_unet_leg)):
             try:
                 res = leg(dev, args)
@@ -1048,7 +1109,7 @@ def main():
                 unet = res
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         cpu = cpu_baseline(model)
 
     watchdog.disarm()

@@ -30,8 +30,8 @@ def _line(stdout: str) -> dict:
 
 def test_single_gpu_line_has_every_contract_field():
     env = dict(os.environ, PYTC_BENCH_VOLUME="165x336x336")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--train-steps", "2", "--no-extras",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--train-steps", "2", "--full",
+                        "--no-extras", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     assert REQUIRED <= set(d), REQUIRED - set(d)
@@ -60,7 +60,7 @@ def test_two_ranks_sharing_the_gpu_run_weak_strong_and_ddp_legs():
     env = dict(os.environ, PYTC_BENCH_SHARE_GPU="1", PYTC_BENCH_VOLUME="165x336x336")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--train-steps", "2", "--train-batch", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--train-steps", "2", "--train-batch", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
@@ -68,3 +68,21 @@ def test_two_ranks_sharing_the_gpu_run_weak_strong_and_ddp_legs():
     assert d["strong_slab"]["scaling"] == "strong" and d["strong_slab"]["seconds"] > 0
     assert d["train"]["parallelism"] == "ddp2" and d["train"]["ms_per_step"] > 0
     assert d["cpu_baseline"] is None or d["cpu_baseline"]["cores"] >= 1      # rank 0 at N = 1 only
+
+
+def test_plain_run_is_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no secondary leg ran) and --dump-outputs writes the last timed step's
+    output: whole for a small volume, float32."""
+    import numpy as np
+    env = dict(os.environ, PYTC_BENCH_VOLUME="120x224x224")
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["full"] is False
+    assert abs(d["timed_region_s"] * 1e3 / 2 - d["ms_per_step"]) < 1e-6 * d["ms_per_step"]
+    assert all(d[k] is None for k in ("roofline", "cpu_baseline", "train", "strong_slab", "rsunet", "monai_unet"))
+    assert not {"tta8", "cube448", "fp32"} & set(d)
+    assert d["dump_outputs"]["arrays"] == {"output": d["output_shape"]}
+    y = np.load(tmp_path / "out" / "output.npy")
+    assert y.dtype == np.float32 and list(y.shape) == d["output_shape"] and np.isfinite(y).all() and y.std() > 0

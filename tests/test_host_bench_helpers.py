@@ -107,3 +107,29 @@ def test_headline_watchdog_prints_the_line_and_leaves(tmp_path):
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0]) == {"value": 42.0, "errors": {"watchdog": {"0": "late"}}}
     assert "never" not in p.stdout
+
+
+def test_plain_run_options_and_output_dump(tmp_path):
+    """A plain run is the headline alone (--full adds the secondary legs); --steps counts timed steps, at least one; dump_outputs writes
+    float32 .npy files within 64 MB: a small output whole, a large one as a seeded sample plus its central z plane."""
+    import numpy as np
+    import pytest
+    import torch
+    b = _bench()
+    a = b.parse_args(["--steps", "3", "--warmup", "0"])
+    assert a.steps == 3 and a.warmup == 0 and a.full is False and a.dump_outputs is None
+    assert b.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full is True
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+    small = torch.rand(1, 1, 16, 24, 32)
+    assert b.dump_outputs(small, tmp_path / "s") == {"output": [1, 1, 16, 24, 32]}
+    got = np.load(tmp_path / "s" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    big = torch.rand(1, 1, 40, 512, 512, generator=torch.Generator().manual_seed(3))
+    shapes = b.dump_outputs(big, tmp_path / "b")
+    assert set(shapes) == {"output_sample", "output_mid_z_plane"} and shapes["output_mid_z_plane"] == [512, 512]
+    files = list((tmp_path / "b").glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    idx = np.unique(np.random.default_rng(b.DUMP_SEED).integers(0, big.numel(), size=b.DUMP_SAMPLE))
+    assert np.array_equal(np.load(tmp_path / "b" / "output_sample.npy"), big.reshape(-1).numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "b" / "output_mid_z_plane.npy"), big[0, 0, 20].numpy())

@@ -152,15 +152,16 @@ train:
         apply_profiles({"shared": {}})
 
 
-@pytest.mark.skipif(not Path("/root/reference/tutorials").exists(), reason="reference checkout not present")
-def test_reference_tutorial_configs_resolve_through_their_own_profile_library():
-    """Drop-in check against the reference's data files where they lie (never copied): every training tutorial loads in train and
-    test mode, its architecture profile picks the right builder, and the loss / activation profiles expand to terms this engine knows."""
+def test_reference_tutorial_configs_resolve_through_their_own_profile_library(golden_dir):
+    """Drop-in check against the reference's data files (stored unchanged under tests/golden/reference_configs/, in the reference's
+    own layout so that each tutorial's `_base_: ../connectomics/config/all_profiles.yaml` resolves): every training tutorial loads in
+    train and test mode, its architecture profile picks the right builder, and the loss / activation profiles expand to terms this
+    engine knows."""
     import warnings
     from pytorch_connectomics_amd.config import load_config
     from pytorch_connectomics_amd.models import build_model
     from pytorch_connectomics_amd.training.module import _LOSSES
-    tut = Path("/root/reference/tutorials")
+    tut = golden_dir / "reference_configs" / "tutorials"
     expect = {"syn_cremi.yaml": "rsunet", "nuc_nucmm-z.yaml": "monai_unet", "minimal.yaml": "monai_unet", "fiber_linghu26.yaml": "mednext",
               "neuron_liconn_mit.yaml": "mednext", "banis.yaml": "mednext"}
     for name, arch in expect.items():

@@ -4,7 +4,7 @@ set -u
 OUT=$PWD/gpurun_out/prof_bench_mfma
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-train"
+CMD="python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-roofline --no-train"
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_WAVES --output-format csv -d $OUT/p1 -o b -- $CMD > $OUT/p1.log 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY --output-format csv -d $OUT/p2 -o b -- $CMD > $OUT/p2.log 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $OUT/p3 -o b -- $CMD > $OUT/p3.log 2>&1

@@ -4,7 +4,7 @@ set -u
 OUT=$PWD/gpurun_out/r06_call1
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-train --no-live-pmc > $OUT/bench.log 2>&1
+timeout 600 python bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-train --no-live-pmc > $OUT/bench.log 2>&1
 grep "^{" $OUT/bench.log | tail -1 > $OUT/bench_line.json
 python - $OUT/bench_line.json <<'PY'
 import json, sys

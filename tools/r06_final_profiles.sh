@@ -1,14 +1,15 @@
 #!/bin/bash
-# round 6: the driver's bench command on the current tree, then the profile passes of tools/profile_r06.sh (bench with one / three window
+# round 6: the bench command with every leg (--full) on the current tree, then the profile passes of tools/profile_r06.sh (bench with one / three window
 # streams, training step: kernel trace + stats, FETCH / WRITE counters)
 set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_bench_driver_cmd.log 2>&1
-grep "^{" gpurun_out/r06_bench_driver_cmd.log | tail -1 > gpurun_out/r06_bench_line.json
-python - <<'PY'
-import json
-d = json.load(open("gpurun_out/r06_bench_line.json"))
+OUT=$PWD/build/bench_r06; mkdir -p $OUT
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/r06_bench_full.log 2>&1
+grep "^{" $OUT/r06_bench_full.log | tail -1 > $OUT/r06_bench_line.json
+python - $OUT/r06_bench_line.json <<'PY'
+import json, sys
+d = json.load(open(sys.argv[1]))
 print("ms/8win", d.get("ms_per_8_windows"), "value", d.get("value"), "roofline", {k: d["roofline"].get(k) for k in ("achieved", "frac", "traffic")})
 print("whole_step", d["roofline"].get("whole_step"))
 print("train", {k: d["train"].get(k) for k in ("value", "ms_per_step")} if d.get("train") else None)
