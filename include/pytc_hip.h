@@ -807,6 +807,25 @@ int pytc_layernorm_rows(const void* x, void* y, const float* gamma, const float*
  * pytc_grn_bwd_apply: out = (dh2 * A[n][c] + gelu(hp) * B[n][c]) * gelu'(hp) on [N][rows][C]: the derivative of
  *   h2 = h * (gamma * nx + 1) + beta, h = gelu(hp), with the per-(sample, channel) coefficients A = gamma * nx + 1 and
  *   B = (dL/dgx) / gx built by the caller from the (N, 2, C) sums of pytc_norm_bwd_stats(dh2, h). */
+/* ---------------------------------------------------------------- MONAI BasicUNet UpCat (csrc/upcat_kernels.hip) ---------- */
+/* Replaces the decoder block of the reference's `monai_basic_unet3d` (connectomics/models/architectures/monai_models.py:142-194 ->
+ * monai.networks.nets.basic_unet.UpCat: UpSample(mode="deconv") = nn.ConvTranspose3d(C_in, C_u, 2, stride 2), F.pad(..., "replicate")
+ * of the up tensor to the skip's size, torch.cat([x_e, x_0], dim=1)) and its torch-autograd backward.  Channels-last, bf16 / fp32
+ * storage, fp32 accumulation; no atomics (bit-reproducible).  x_low (N, d, h, w, C_in), x_e / cat / dcat on (N, D, H, W) with
+ * D in {2d, 2d + 1} (and H, W alike); w the ConvTranspose3d weight, fp32 (C_in, C_u, 2, 2, 2); bias fp32 (C_u) or null.
+ * pytc_upcat_deconv2_fwd: cat[..., :C_e] = x_e, cat[2z+a, 2y+b, 2x+c, C_e + o] = bias[o] + sum_i x_low[z, y, x, i] W[i, o, a, b, c],
+ *   on an odd axis the last plane repeats the one before it.  One MFMA GEMM (rows x C_in by C_in x 8 C_u) with a scatter epilogue.
+ * pytc_upcat_deconv2_bwd_data: dx_e = dcat[..., :C_e] (dx_e nullable); dx_low = G . W^T (dx_low nullable), G = dcat[..., C_e:] gathered
+ *   at the eight children with the replicated faces folded into the last plane.
+ * pytc_upcat_deconv2_wgrad: dw fp32 (C_in, C_u, 2, 2, 2) = x_low^T . G, db fp32 (C_u, nullable) = sum G; split-K partials in
+ *   `workspace` (pytc_upcat_deconv2_wgrad_ws_elems floats) reduced in a fixed order. */
+int pytc_upcat_deconv2_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* cat, int N, int d, int h, int wd,
+                           int D, int H, int W, int C_in, int C_e, int C_u, int dtype, void* stream);
+int pytc_upcat_deconv2_bwd_data(const void* dcat, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd, int D, int H,
+                                int W, int C_in, int C_e, int C_u, int dtype, void* stream);
+int64_t pytc_upcat_deconv2_wgrad_ws_elems(int rows, int C_in, int C_u, int dtype);
+int pytc_upcat_deconv2_wgrad(const void* x_low, const void* dcat, float* workspace, float* dw, float* db, int N, int d, int h, int wd,
+                             int D, int H, int W, int C_in, int C_e, int C_u, int dtype, void* stream);
 int pytc_layernorm_rows_bwd_slots(int64_t rows, int C, int dtype);
 int pytc_layernorm_rows_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* partial, int64_t rows, int C,
                             float eps, int dtype, void* stream);

@@ -272,6 +272,10 @@ _SIGS = {
     "pytc_pw_mlp_up_fwd": (C.c_int, [C.POINTER(MlpArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pytc_pw_mlp_head_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "pytc_pw_mlp_head_fwd": (C.c_int, [C.POINTER(MlpArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "pytc_upcat_deconv2_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p]),
+    "pytc_upcat_deconv2_bwd_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p]),
+    "pytc_upcat_deconv2_wgrad_ws_elems": (C.c_int64, [C.c_int] * 4),
+    "pytc_upcat_deconv2_wgrad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 11 + [C.c_void_p]),
 }
 
 _lib = None

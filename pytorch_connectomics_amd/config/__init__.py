@@ -69,7 +69,7 @@ def schema_defaults() -> dict:
                  # schema/data.py: batch_size 4 (also the sliding-window batch when sw_batch_size is unset, window.py:413-423) and image
                  # normalisation "0-1" are the reference's defaults -- tutorials such as mito_lucchi++ rely on them unnamed.  NOT taken
                  # over: dataloader.patch_size / model.input_size / model.output_size = [128, 128, 128] (here None: a configuration
-                 # names its patch and window sizes) and model.arch.type = monai_basic_unet3d (outside the hot path; here mednext)
+                 # names its patch and window sizes) and model.arch.type = monai_basic_unet3d (built here too, but the default stays mednext)
                  "dataloader": {"batch_size": 4, "patch_size": None, "use_lazy_zarr": False, "use_lazy_h5": False},
                  "data_transform": {"patch_size": None},
                  "image_transform": {"transform_profile": None, "normalize": "0-1", "clip_percentile_low": 0.0, "clip_percentile_high": 1.0},

@@ -1269,6 +1269,62 @@ def maxpool3d(x: torch.Tensor, factor) -> torch.Tensor:
     return y
 
 
+def _upcat_dims(x_low: torch.Tensor, skip_shape) -> list:
+    N, d, h, w, C_in = x_low.shape
+    D, H, W = (int(v) for v in skip_shape[1:4])
+    for lo, hi, axis in ((d, D, "D"), (h, H, "H"), (w, W, "W")):
+        if hi not in (2 * lo, 2 * lo + 1):
+            raise ValueError(f"upcat: skip axis {axis} = {hi} is neither 2x nor 2x + 1 the up-sampled input's {lo}")
+    return [N, d, h, w, D, H, W]
+
+
+def upcat_deconv2_fwd(x_low: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], x_e: torch.Tensor) -> torch.Tensor:
+    """MONAI UpCat in one buffer: cat = [x_e, pad_replicate(conv_transpose3d(x_low, weight, bias, stride 2))] on channels-last
+    tensors; weight fp32 (C_in, C_u, 2, 2, 2) (csrc/upcat_kernels.hip)."""
+    _dev(x_low, "x_low"), _dev(x_e, "x_e"), _dev(weight, "weight")
+    if x_e.dtype != x_low.dtype or weight.dtype != torch.float32:
+        raise TypeError("upcat_deconv2_fwd: x_e must match x_low's dtype and the weight must be fp32")
+    dims = _upcat_dims(x_low, x_e.shape)
+    C_in, C_e, C_u = int(x_low.shape[-1]), int(x_e.shape[-1]), int(weight.shape[1])
+    if tuple(weight.shape) != (C_in, C_u, 2, 2, 2):
+        raise ValueError(f"upcat_deconv2_fwd: weight {tuple(weight.shape)} is not a ({C_in}, C_u, 2, 2, 2) ConvTranspose3d weight")
+    cat = torch.empty((*x_e.shape[:4], C_e + C_u), dtype=x_e.dtype, device=x_e.device)
+    rows = x_low.numel() // C_in
+    _run(f"upcat_deconv2_fwd[{C_in}->{C_u}+{C_e}]", _nbytes(x_low, x_e, cat, weight), nat.lib().pytc_upcat_deconv2_fwd, _p(x_low),
+         _p(weight), _p(bias), _p(x_e), _p(cat), *dims, C_in, C_e, C_u, dtype_code(x_low.dtype), _stream(),
+         flops=2 * rows * C_in * 8 * C_u, symbol="upcat_deconv2_fwd")
+    return cat
+
+
+def upcat_deconv2_bwd(dcat: torch.Tensor, x_low: torch.Tensor, weight: torch.Tensor, C_e: int, want_dx_e: bool = True,
+                      want_dx_low: bool = True, want_w: bool = True, want_b: bool = True):
+    """Backward of upcat_deconv2_fwd -> (dx_e, dx_low, dW fp32, db fp32), each None when not wanted."""
+    _dev(dcat, "dcat"), _dev(x_low, "x_low"), _dev(weight, "weight")
+    dims = _upcat_dims(x_low, dcat.shape)
+    C_in, C_u = int(x_low.shape[-1]), int(weight.shape[1])
+    if int(dcat.shape[-1]) != C_e + C_u or dcat.dtype != x_low.dtype:
+        raise ValueError(f"upcat_deconv2_bwd: dcat {tuple(dcat.shape)} {dcat.dtype} does not fit C_e = {C_e} + C_u = {C_u}")
+    dt = dtype_code(x_low.dtype)
+    rows = x_low.numel() // C_in
+    dx_e = torch.empty((*dcat.shape[:4], C_e), dtype=dcat.dtype, device=dcat.device) if want_dx_e else None
+    dx_low = torch.empty_like(x_low) if want_dx_low else None
+    if dx_e is not None or dx_low is not None:
+        _run(f"upcat_deconv2_bwd_data[{C_in}<-{C_u}+{C_e}]", _nbytes(dcat, dx_e, dx_low, weight), nat.lib().pytc_upcat_deconv2_bwd_data,
+             _p(dcat), _p(weight), _p(dx_e), _p(dx_low), *dims, C_in, C_e, C_u, dt, _stream(),
+             flops=2 * rows * C_in * 8 * C_u if want_dx_low else 0, symbol="upcat_deconv2_bwd_data")
+    dW = db = None
+    if want_w or want_b:
+        ws = torch.empty((int(nat.lib().pytc_upcat_deconv2_wgrad_ws_elems(rows, C_in, C_u, dt)),), dtype=torch.float32, device=dcat.device)
+        dW = torch.empty((C_in, C_u, 2, 2, 2), dtype=torch.float32, device=dcat.device)
+        db = torch.empty((C_u,), dtype=torch.float32, device=dcat.device) if want_b else None
+        _run(f"upcat_deconv2_wgrad[{C_in}x{C_u}]", _nbytes(x_low, dcat, ws, ws), nat.lib().pytc_upcat_deconv2_wgrad, _p(x_low), _p(dcat),
+             _p(ws), _p(dW), _p(db), *dims, C_in, C_e, C_u, dt, _stream(), flops=2 * rows * (C_in + 1) * 8 * C_u,
+             symbol="upcat_deconv2_wgrad")
+        if not want_w:
+            dW = None
+    return dx_e, dx_low, dW, db
+
+
 def dwconvT3d_generic(x: torch.Tensor, w_taps: torch.Tensor, kernel, stride, pad) -> torch.Tensor:
     """Depthwise transposed conv with per-axis geometry; w_taps fp32 (kd*kh*kw, C)."""
     _dev(x, "x")

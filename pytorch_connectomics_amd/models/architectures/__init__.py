@@ -4,7 +4,7 @@ from .registry import (get_architecture_builder, get_architecture_info, is_archi
                        list_architectures, register_architecture, unregister_architecture)
 from . import mednext_models  # noqa: F401  (registers 'mednext', 'mednext_custom')
 from . import rsunet  # noqa: F401          (registers 'rsunet', 'rsunet_iso')
-from . import monai_models  # noqa: F401    (registers 'monai_unet')
+from . import monai_models  # noqa: F401    (registers 'monai_unet', 'monai_basic_unet3d')
 from .mednext_models import MedNeXtMultiHeadWrapper, MedNeXtTaskHead, MedNeXtWrapper
 
 

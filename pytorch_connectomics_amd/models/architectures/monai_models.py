@@ -19,6 +19,12 @@ The torch.nn children are parameter holders.  `forward` runs hand-written gfx950
 autograd Functions of training/rsunet_autograd.py (dense conv3d on MFMA; the stride-2 / transposed resampling convs
 in csrc/conv3d_strided_kernels.hip; norm statistics, affine + PReLU, their backward kernels), in training and inference.
 No CPU path.
+
+`monai_basic_unet3d` (build_basic_unet, reference monai_models.py:142-194) restates monai.networks.nets.BasicUNet the same way
+(`model.conv_0.conv_0.conv.weight`, `model.down_1.convs.conv_1.adn.N.running_mean`, `model.upcat_4.upsample.deconv.weight`,
+`model.final_conv.weight`): TwoConv / Down(MaxPool3d 2, TwoConv) / UpCat(deconv k2 s2 -> replicate pad to the skip -> cat([skip, up])
+-> TwoConv), ADN = norm -> dropout -> relu | leakyrelu | prelu | elu.  Each UpCat's deconv, pad and concat are ONE fused kernel pair
+(csrc/upcat_kernels.hip through training/rsunet_autograd.py UpCatFn).
 """
 from __future__ import annotations
 
@@ -55,22 +61,38 @@ def _make_norm(norm, channels: int) -> nn.Module:
     raise ValueError(f"Unsupported MONAI norm {norm!r} for the MI355X engine (batch, instance, group)")
 
 
+_ACTS = {"relu": nn.ReLU, "leakyrelu": nn.LeakyReLU, "prelu": nn.PReLU, "elu": nn.ELU}
+
+
+def _make_act(act) -> nn.Module:
+    """MONAI activation factory for the four activations the norm + activation kernels implement: a name, or (name, kwargs) as MONAI
+    spells it; defaults are torch's (LeakyReLU slope 0.01, PReLU one weight 0.25, ELU alpha 1)."""
+    args = {}
+    if isinstance(act, (tuple, list)):
+        act, args = act[0], {k: v for k, v in dict(act[1]).items() if k != "inplace"}
+    name = str(act).lower()
+    if name not in _ACTS:
+        raise NotImplementedError(f"MONAI activation {act!r} has no HIP kernel (supported: {', '.join(_ACTS)})")
+    return _ACTS[name](**args)
+
+
 class ADN(nn.Sequential):
     """norm -> dropout -> activation ("NDA"), children named N / D / A as in monai.networks.blocks.ADN."""
 
-    def __init__(self, channels: int, norm, dropout: Optional[float]):
+    def __init__(self, channels: int, norm, dropout: Optional[float], act="prelu"):
         super().__init__()
         self.add_module("N", _make_norm(norm, channels))
         if dropout is not None:
             self.add_module("D", nn.Dropout(float(dropout)))
-        self.add_module("A", nn.PReLU())
+        self.add_module("A", _make_act(act))
 
 
 class Convolution(nn.Sequential):
     """conv (or transposed conv) [+ ADN] -- monai.networks.blocks.Convolution for spatial_dims = 3."""
 
     def __init__(self, in_channels: int, out_channels: int, strides: int = 1, kernel_size: int = 3, norm="instance",
-                 dropout: Optional[float] = None, bias: bool = True, conv_only: bool = False, is_transposed: bool = False):
+                 dropout: Optional[float] = None, bias: bool = True, conv_only: bool = False, is_transposed: bool = False,
+                 act="prelu"):
         super().__init__()
         pad = _same_padding(kernel_size)
         if is_transposed:
@@ -80,7 +102,7 @@ class Convolution(nn.Sequential):
             conv = nn.Conv3d(in_channels, out_channels, kernel_size, stride=strides, padding=pad, bias=bias)
         self.add_module("conv", conv)
         if not conv_only:
-            self.add_module("adn", ADN(out_channels, norm, dropout))
+            self.add_module("adn", ADN(out_channels, norm, dropout, act))
 
 
 class ResidualUnit(nn.Module):
@@ -194,8 +216,17 @@ def _adn(adn: ADN, x: torch.Tensor) -> torch.Tensor:
         kind, groups, bn = "group", n.num_groups, None
     else:
         kind, groups, bn = "instance", 1, None
-    return NormActFn.apply(x, getattr(n, "weight", None), getattr(n, "bias", None), adn.A.weight, kind, groups,
-                           float(n.eps), "prelu", 0.0, bn)
+    a = adn.A
+    if isinstance(a, nn.PReLU):
+        act_kind, prm, prelu_w = "prelu", 0.0, a.weight
+    elif isinstance(a, nn.LeakyReLU):
+        act_kind, prm, prelu_w = "leakyrelu", float(a.negative_slope), None
+    elif isinstance(a, nn.ELU):
+        act_kind, prm, prelu_w = "elu", float(a.alpha), None
+    else:
+        act_kind, prm, prelu_w = "relu", 0.0, None
+    return NormActFn.apply(x, getattr(n, "weight", None), getattr(n, "bias", None), prelu_w, kind, groups,
+                           float(n.eps), act_kind, prm, bn)
 
 
 def _convolution(m: Convolution, x: torch.Tensor) -> torch.Tensor:
@@ -238,6 +269,109 @@ def _run(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
     raise TypeError(f"unexpected module in the MONAI U-Net tree: {type(mod).__name__}")
 
 
+# ------------------------------------------------------------------------------------------------------ MONAI BasicUNet
+class TwoConv(nn.Sequential):
+    """monai.networks.nets.basic_unet.TwoConv: two Convolution(k3, p1) -> ADN ("NDA") units."""
+
+    def __init__(self, in_chns: int, out_chns: int, act, norm, bias: bool, dropout: float = 0.0):
+        super().__init__()
+        self.add_module("conv_0", Convolution(in_chns, out_chns, norm=norm, dropout=dropout, bias=bias, act=act))
+        self.add_module("conv_1", Convolution(out_chns, out_chns, norm=norm, dropout=dropout, bias=bias, act=act))
+
+
+class Down(nn.Sequential):
+    """monai.networks.nets.basic_unet.Down: MaxPool3d(2) -> TwoConv."""
+
+    def __init__(self, in_chns: int, out_chns: int, act, norm, bias: bool, dropout: float = 0.0):
+        super().__init__()
+        self.add_module("max_pooling", nn.MaxPool3d(kernel_size=2))
+        self.add_module("convs", TwoConv(in_chns, out_chns, act, norm, bias, dropout))
+
+
+class UpSample(nn.Sequential):
+    """monai.networks.blocks.UpSample(mode="deconv", scale_factor=2): one ConvTranspose3d(k 2, stride 2) named `deconv`."""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool = True):
+        super().__init__()
+        self.add_module("deconv", nn.ConvTranspose3d(in_channels, out_channels, kernel_size=2, stride=2, bias=bias))
+
+
+class UpCat(nn.Module):
+    """monai.networks.nets.basic_unet.UpCat: up-sample, replicate-pad to the skip's size, cat([skip, up]), TwoConv."""
+
+    def __init__(self, in_chns: int, cat_chns: int, out_chns: int, act, norm, bias: bool, dropout: float = 0.0,
+                 upsample: str = "deconv", halves: bool = True):
+        super().__init__()
+        if upsample != "deconv":
+            raise NotImplementedError(f"monai_basic_unet3d upsample_mode={upsample!r}: only 'deconv' has HIP kernels "
+                                      "('nontrainable' and 'pixelshuffle' are not built)")
+        up_chns = in_chns // 2 if halves else in_chns
+        self.upsample = UpSample(in_chns, up_chns, bias)
+        self.convs = TwoConv(cat_chns + up_chns, out_chns, act, norm, bias, dropout)
+
+
+class BasicUNet(nn.Module):
+    """monai.networks.nets.BasicUNet (spatial_dims = 3) with the same child names, so state-dict keys interchange."""
+
+    def __init__(self, spatial_dims: int = 3, in_channels: int = 1, out_channels: int = 2,
+                 features: Sequence[int] = (32, 32, 64, 128, 256, 32), act="relu", norm="batch", bias: bool = True,
+                 dropout: float = 0.0, upsample: str = "deconv"):
+        super().__init__()
+        if spatial_dims != 3:
+            raise NotImplementedError("the MI355X engine builds the 3-D MONAI BasicUNet only (spatial_dims=3)")
+        if upsample != "deconv":
+            raise NotImplementedError(f"monai_basic_unet3d upsample_mode={upsample!r}: only 'deconv' has HIP kernels "
+                                      "('nontrainable' and 'pixelshuffle' are not built)")
+        fea = tuple(int(f) for f in features)
+        if len(fea) != 6:
+            raise ValueError(f"BasicUNet needs 6 feature sizes, got {len(fea)}")
+        self.features = fea
+        self.conv_0 = TwoConv(in_channels, fea[0], act, norm, bias, dropout)
+        self.down_1 = Down(fea[0], fea[1], act, norm, bias, dropout)
+        self.down_2 = Down(fea[1], fea[2], act, norm, bias, dropout)
+        self.down_3 = Down(fea[2], fea[3], act, norm, bias, dropout)
+        self.down_4 = Down(fea[3], fea[4], act, norm, bias, dropout)
+        self.upcat_4 = UpCat(fea[4], fea[3], fea[3], act, norm, bias, dropout, upsample)
+        self.upcat_3 = UpCat(fea[3], fea[2], fea[2], act, norm, bias, dropout, upsample)
+        self.upcat_2 = UpCat(fea[2], fea[1], fea[1], act, norm, bias, dropout, upsample)
+        self.upcat_1 = UpCat(fea[1], fea[0], fea[5], act, norm, bias, dropout, upsample, halves=False)
+        self.final_conv = nn.Conv3d(fea[5], out_channels, kernel_size=1)
+
+    def forward(self, x):  # pragma: no cover - guard only
+        raise RuntimeError("the MONAI-style BasicUNet executes through MONAIModelWrapper.forward (HIP engine); its modules are "
+                           "parameter holders")
+
+
+def _two_conv(m: TwoConv, x: torch.Tensor) -> torch.Tensor:
+    return _convolution(m.conv_1, _convolution(m.conv_0, x))
+
+
+def _up_cat(m: UpCat, x_low: torch.Tensor, x_e: torch.Tensor) -> torch.Tensor:
+    from ...training.rsunet_autograd import UpCatFn
+    d = m.upsample.deconv
+    return _two_conv(m.convs, UpCatFn.apply(x_e, x_low, d.weight, d.bias))
+
+
+def basic_unet_forward(net: BasicUNet, x: torch.Tensor) -> torch.Tensor:
+    """BasicUNet on channels-last x (N, D, H, W, C): TwoConv / MaxPool / fused UpCat / 1x1 conv, every piece a HIP kernel with its own
+    autograd backward; nothing is built lazily or shared between calls (safe on the window engine's side streams)."""
+    from ...training.rsunet_autograd import MaxPoolFn, ResampleConv3dFn
+    for axis, size in zip("DHW", x.shape[1:4]):
+        if int(size) < 16:
+            raise ValueError(f"monai_basic_unet3d: spatial axis {axis} has {int(size)} voxels; four 2x max-poolings need at least 16")
+    x0 = _two_conv(net.conv_0, x)
+    x1 = _two_conv(net.down_1.convs, MaxPoolFn.apply(x0, (2, 2, 2)))
+    x2 = _two_conv(net.down_2.convs, MaxPoolFn.apply(x1, (2, 2, 2)))
+    x3 = _two_conv(net.down_3.convs, MaxPoolFn.apply(x2, (2, 2, 2)))
+    x4 = _two_conv(net.down_4.convs, MaxPoolFn.apply(x3, (2, 2, 2)))
+    u = _up_cat(net.upcat_4, x4, x3)
+    u = _up_cat(net.upcat_3, u, x2)
+    u = _up_cat(net.upcat_2, u, x1)
+    u = _up_cat(net.upcat_1, u, x0)
+    f = net.final_conv
+    return ResampleConv3dFn.apply(u, f.weight, f.bias, 1, 0, False)
+
+
 class MONAIModelWrapper(ConnectomicsModel):
     """ConnectomicsModel interface over the MONAI-style network; single-scale output (no deep supervision)."""
 
@@ -251,21 +385,28 @@ class MONAIModelWrapper(ConnectomicsModel):
     def forward_cl(self, x_cl: torch.Tensor) -> torch.Tensor:
         """Channels-last entry of the sliding-window engine: (N,D,H,W,C_in) -> (N,D,H,W,C_out) fp32."""
         if not x_cl.is_cuda:
-            raise RuntimeError("monai_unet (pytorch_connectomics_amd) runs only on an MI355X/ROCm device: "
+            raise RuntimeError(f"{self._arch} (pytorch_connectomics_amd) runs only on an MI355X/ROCm device: "
                                "there is no CPU path. Move the model and input to 'cuda'.")
         from ...training.rsunet_autograd import prefetch_prelu, refresh_conv_packs
         prefetch_prelu([m.weight for m in self.model.modules() if isinstance(m, nn.PReLU)])   # one host read, not one per layer
         refresh_conv_packs()          # every conv-weight image whose weight changed since the last forward, in one launch
         dt = resolve_compute_dtype(self.compute_dtype)
         x = x_cl if x_cl.dtype == dt else x_cl.to(dt)
+        if isinstance(self.model, BasicUNet):
+            return basic_unet_forward(self.model, x.contiguous()).float()
         return _run(self.model.model, x.contiguous()).float()
+
+    @property
+    def _arch(self) -> str:
+        return "monai_basic_unet3d" if isinstance(self.model, BasicUNet) else "monai_unet"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:
-            raise RuntimeError("monai_unet (pytorch_connectomics_amd) runs only on an MI355X/ROCm device: "
+            raise RuntimeError(f"{self._arch} (pytorch_connectomics_amd) runs only on an MI355X/ROCm device: "
                                "there is no CPU path. Move the model and input to 'cuda'.")
         if x.dim() != 5:
-            raise NotImplementedError("the MI355X engine runs the 3-D MONAI U-Net on (B, C, D, H, W) inputs")
+            raise NotImplementedError(f"the MI355X engine runs the 3-D MONAI {'BasicUNet' if isinstance(self.model, BasicUNet) else 'U-Net'}"
+                                      " on (B, C, D, H, W) inputs")
         y = self.forward_cl(to_channels_last(x.float()))
         return y.permute(0, 4, 1, 2, 3) if y.requires_grad else to_channels_first(y)
 
@@ -281,6 +422,29 @@ def _resolve_norm(cfg):
     if norm_type == "group":
         return ("group", {"num_groups": getattr(cfg.model.monai, "num_groups", 8)})
     return norm_type
+
+
+def _basic_unet_features(filters) -> tuple:
+    """BasicUNet takes exactly six feature sizes: pad with the last value repeated, then truncate (monai_models.py:178-182)."""
+    fea = [int(f) for f in filters]
+    if not fea:
+        raise ValueError("model.monai.filters must not be empty")
+    while len(fea) < 6:
+        fea.append(fea[-1])
+    return tuple(fea[:6])
+
+
+@register_architecture("monai_basic_unet3d")
+def build_basic_unet(cfg) -> ConnectomicsModel:
+    """MONAI BasicUNet: model.monai.{filters (padded / truncated to 6), dropout, activation, norm, num_groups, upsample_mode};
+    (monai_models.py:142-194).  Only upsample_mode='deconv' is built."""
+    mc = cfg.model.monai
+    model = BasicUNet(
+        spatial_dims=_infer_spatial_dims(cfg), in_channels=cfg.model.in_channels, out_channels=cfg.model.out_channels,
+        features=_basic_unet_features(getattr(mc, "filters", [32, 64, 128, 256, 512])),
+        dropout=getattr(mc, "dropout", 0.0), act=getattr(mc, "activation", "relu"), norm=_resolve_norm(cfg),
+        upsample=getattr(mc, "upsample_mode", "deconv"))
+    return MONAIModelWrapper(model)
 
 
 @register_architecture("monai_unet")
@@ -300,4 +464,4 @@ def build_monai_unet(cfg) -> ConnectomicsModel:
 
 
 __all__ = ["MONAIModelWrapper", "UpsampleModeUNet", "UNet", "ResidualUnit", "Convolution", "ADN", "SkipConnection",
-           "build_monai_unet"]
+           "BasicUNet", "TwoConv", "Down", "UpSample", "UpCat", "basic_unet_forward", "build_basic_unet", "build_monai_unet"]

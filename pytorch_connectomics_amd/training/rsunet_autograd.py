@@ -355,6 +355,33 @@ class ResampleConv3dFn(torch.autograd.Function):
         return da, dW.to(weight.dtype), db, None, None, None
 
 
+class UpCatFn(torch.autograd.Function):
+    """MONAI UpCat with mode="deconv": cat = [x_e, pad_replicate(ConvTranspose3d(k 2, s 2, p 0)(x_low))] along the channels, on
+    channels-last tensors, written by ONE kernel pair into the concat buffer (csrc/upcat_kernels.hip).  Backward: dx_e = the skip's
+    channel slice, dx_low / dW / db from the up half gathered at the eight children with the replicated faces folded back."""
+
+    @staticmethod
+    def forward(ctx, x_e, x_low, weight, bias):
+        x_low = x_low.contiguous()
+        x_e = x_e.contiguous() if x_e.dtype == x_low.dtype else x_e.to(x_low.dtype).contiguous()
+        cat = ops.upcat_deconv2_fwd(x_low, weight.detach().float().contiguous(), _f(bias), x_e)
+        ctx.save_for_backward(x_low, weight)
+        ctx.meta = (int(x_e.shape[-1]), bias is not None, x_e.dtype)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        x_low, weight = ctx.saved_tensors
+        C_e, has_bias, e_dtype = ctx.meta
+        dcat = dcat.contiguous()
+        if dcat.dtype != x_low.dtype:
+            dcat = dcat.to(x_low.dtype)
+        need = ctx.needs_input_grad
+        dx_e, dx_low, dW, db = ops.upcat_deconv2_bwd(dcat, x_low, weight.detach().float().contiguous(), C_e, want_dx_e=need[0],
+                                                     want_dx_low=need[1], want_w=need[2], want_b=has_bias and need[3])
+        return (dx_e, dx_low, None if dW is None else dW.to(weight.dtype), None if db is None else db.to(weight.dtype))
+
+
 class AddFn(torch.autograd.Function):
     """y = a + b (the residual sum of a MONAI ResidualUnit) with the HIP add kernel; both gradients are dy."""
 
@@ -431,4 +458,4 @@ def rsunet_train_forward(model, x_cl: torch.Tensor, compute_dtype: torch.dtype):
     return out
 
 
-__all__ = ["NormActFn", "Conv3dFn", "ResampleConv3dFn", "AddFn", "MaxPoolFn", "UpsampleFn", "rsunet_train_forward"]
+__all__ = ["NormActFn", "Conv3dFn", "ResampleConv3dFn", "UpCatFn", "AddFn", "MaxPoolFn", "UpsampleFn", "rsunet_train_forward"]
