@@ -826,6 +826,46 @@ int pytc_upcat_deconv2_bwd_data(const void* dcat, const float* w, void* dx_e, vo
 int64_t pytc_upcat_deconv2_wgrad_ws_elems(int rows, int C_in, int C_u, int dtype);
 int pytc_upcat_deconv2_wgrad(const void* x_low, const void* dcat, float* workspace, float* dw, float* db, int N, int d, int h, int wd,
                              int D, int H, int W, int C_in, int C_e, int C_u, int dtype, void* stream);
+/* ---------------------------------------------------------------- MONAI UNETR ViT encoder (csrc/transformer_kernels.hip) ---- */
+/* Replaces the ViT of the reference's `monai_unetr` (connectomics/models/architectures/monai_models.py:253-294 -> monai.networks.nets
+ * UNETR / ViT / PatchEmbeddingBlock / TransformerBlock) and its torch-autograd backward.  Token matrices are row-major (B * N, h),
+ * bf16 / fp32 storage, fp32 accumulation; weights and per-channel vectors fp32.  No atomics (bit-reproducible).
+ * pytc_linear_fwd: y[M][N] = f(x)[M][K] . w[N][K]^T (+ bias[N]) (+ pos[m % pos_rows][N]) (+ res[M][N]), f = GELU when x_gelu (x is
+ *   then the stored pre-activation).  pytc_linear_bwd_data: dx[M][K] = dy[M][N] . w[N][K], times gelu'(x_gelu) when x_gelu (the
+ *   pre-activation) is non-null.  pytc_linear_wgrad: dw fp32 [N][K] = dy^T . f(x), db fp32 [N] = sum_m dy, dpos fp32 [pos_rows][N] =
+ *   sum over the batch of dy (each nullable), fixed-order sums.
+ * pytc_layernorm_wide: nn.LayerNorm over rows of C = 64 k <= 1024 channels.  pytc_layernorm_wide_bwd: dx, and dgamma / dbeta
+ *   (nullable) from pytc_layernorm_wide_bwd_slots(rows) fixed-order partials of 2 C floats each in `partial`.
+ * pytc_patch_gather16: scatter 0: dst (B * n_tok, 4096 C) = the 16^3 patches of channels-last src (B, D, H, W, C) in MONAI's
+ *   (p1 p2 p3 c) order, tokens row-major over (D / 16, H / 16, W / 16); scatter 1: the inverse (src = patches, dst = volume).
+ * pytc_attention_fwd: per (batch, head) O = softmax(Q K^T * scale) V with Q / K / V read from qkv (B * N, 3 heads d) in the
+ *   (qkv, head, d) column order, O written as (B * N, heads d) in (head, d) order, lse fp32 (B, heads, N).  d_head in {32, 64}
+ *   (pytc_attention_supported).  pytc_attention_bwd: dqkv (B * N, 3 heads d) from dout; dvec is fp32 scratch of B heads N floats.
+ * pytc_deconv2_upfirst_{fwd,bwd_data,wgrad}: ConvTranspose3d(k 2, s 2) into channels [0, C_u) of out (N, 2d, 2h, 2w, C_u + C_e) with
+ *   x_e copied to channels [C_u, C_u + C_e) -- torch.cat((up, skip), 1) of MONAI's UnetrUpBlock; C_e = 0 is the plain deconv.  The
+ *   weight-gradient workspace holds pytc_upcat_deconv2_wgrad_ws_elems(N d h w, C_in, C_u, dtype) floats. */
+int pytc_linear_fwd(const void* x, const float* w, const float* bias, const float* pos, int pos_rows, const void* res, void* y, int M,
+                    int N, int K, int x_gelu, int dtype, void* stream);
+int pytc_linear_bwd_data(const void* dy, const float* w, const void* x_gelu, void* dx, int M, int N, int K, int dtype, void* stream);
+int pytc_linear_wgrad(const void* dy, const void* x, float* dw, float* db, float* dpos, int pos_rows, int M, int N, int K, int x_gelu,
+                      int dtype, void* stream);
+int pytc_layernorm_wide(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps, int dtype,
+                        void* stream);
+int pytc_layernorm_wide_bwd_slots(int64_t rows);
+int pytc_layernorm_wide_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* partial, float* dgamma, float* dbeta,
+                            int64_t rows, int C, float eps, int dtype, void* stream);
+int pytc_patch_gather16(const void* src, void* dst, int B, int D, int H, int W, int C, int scatter, int dtype, void* stream);
+int pytc_attention_supported(int d_head);
+int pytc_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, int d_head, float scale, int dtype,
+                       void* stream);
+int pytc_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, int B, int N,
+                       int heads, int d_head, float scale, int dtype, void* stream);
+int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* out, int N, int d, int h,
+                             int wd, int C_in, int C_e, int C_u, int dtype, void* stream);
+int pytc_deconv2_upfirst_bwd_data(const void* dout, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd, int C_in,
+                                  int C_e, int C_u, int dtype, void* stream);
+int pytc_deconv2_upfirst_wgrad(const void* x_low, const void* dout, float* workspace, float* dw, float* db, int N, int d, int h, int wd,
+                               int C_in, int C_e, int C_u, int dtype, void* stream);
 int pytc_layernorm_rows_bwd_slots(int64_t rows, int C, int dtype);
 int pytc_layernorm_rows_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* partial, int64_t rows, int C,
                             float eps, int dtype, void* stream);

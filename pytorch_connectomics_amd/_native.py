@@ -276,6 +276,19 @@ _SIGS = {
     "pytc_upcat_deconv2_bwd_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 11 + [C.c_void_p]),
     "pytc_upcat_deconv2_wgrad_ws_elems": (C.c_int64, [C.c_int] * 4),
     "pytc_upcat_deconv2_wgrad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 11 + [C.c_void_p]),
+    "pytc_linear_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "pytc_linear_bwd_data": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "pytc_linear_wgrad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "pytc_layernorm_wide": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "pytc_layernorm_wide_bwd_slots": (C.c_int, [C.c_int64]),
+    "pytc_layernorm_wide_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "pytc_patch_gather16": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p]),
+    "pytc_attention_supported": (C.c_int, [C.c_int]),
+    "pytc_attention_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
+    "pytc_attention_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
+    "pytc_deconv2_upfirst_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
+    "pytc_deconv2_upfirst_bwd_data": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
+    "pytc_deconv2_upfirst_wgrad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
 }
 
 _lib = None

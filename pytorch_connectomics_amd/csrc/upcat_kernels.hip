@@ -41,6 +41,7 @@ struct UpcatParams {
   void* out;             // FWD: cat; DGRAD: dx_low [rows][C_in]; WGRAD: fp32 partials [S][C_in + 1][8 C_u]
   int N, d, h, w_, D, H, W;
   int C_in, C_e, C_u;
+  int up_off, Ct;        // channel offset of the up half and row stride of the concat buffer ([skip, up]: C_e, C_e + C_u)
   int rows;              // N * d * h * w
   int rows_per_split;    // WGRAD: K range of one split (multiple of the k step)
 };
@@ -65,11 +66,11 @@ __device__ __forceinline__ void upcat_row_info(const UpcatParams& p, int r, int&
 template <typename T>
 __device__ __forceinline__ float upcat_gather(const UpcatParams& p, int vbase, int flags, int par, int o) {
   const int a = par >> 2, b = (par >> 1) & 1, c = par & 1;
-  const int Ct = p.C_e + p.C_u;
+  const int Ct = p.Ct;
   const int HW = p.H * p.W;
   const int v = vbase + a * HW + b * p.W + c;
   const int ez = (a & flags) ? 1 : 0, ey = (b && (flags & 2)) ? 1 : 0, ex = (c && (flags & 4)) ? 1 : 0;
-  const T* g = reinterpret_cast<const T*>(p.dcat) + p.C_e + o;
+  const T* g = reinterpret_cast<const T*>(p.dcat) + p.up_off + o;
   float s = 0.f;
   for (int zz = 0; zz <= ez; ++zz)
     for (int yy = 0; yy <= ey; ++yy)
@@ -208,11 +209,11 @@ __global__ void __launch_bounds__(256, 2) upcat_gemm_kernel(UpcatParams p) {
           const int par = P / p.C_u, o = P - par * p.C_u;
           const int a = par >> 2, b = (par >> 1) & 1, c = par & 1;
           const int fl = sFl[ql];
-          const int HW = p.H * p.W, Ct = p.C_e + p.C_u;
+          const int HW = p.H * p.W, Ct = p.Ct;
           const int vx = sVb[ql] + a * HW + b * p.W + c;
           const int ez = (a & fl) ? 1 : 0, ey = (b && (fl & 2)) ? 1 : 0, ex = (c && (fl & 4)) ? 1 : 0;
           const T out = from_f32<T>(val + (p.bias ? p.bias[o] : 0.f));
-          T* dst = reinterpret_cast<T*>(p.out) + p.C_e + o;
+          T* dst = reinterpret_cast<T*>(p.out) + p.up_off + o;
           for (int zz = 0; zz <= ez; ++zz)
             for (int yy = 0; yy <= ey; ++yy)
               for (int xx = 0; xx <= ex; ++xx) dst[(long)(vx + zz * HW + yy * p.W + xx) * Ct] = out;
@@ -281,6 +282,7 @@ static UpcatParams upcat_params(int N, int d, int h, int w, int D, int H, int W,
   memset(&p, 0, sizeof(p));
   p.N = N; p.d = d; p.h = h; p.w_ = w; p.D = D; p.H = H; p.W = W;
   p.C_in = C_in; p.C_e = C_e; p.C_u = C_u;
+  p.up_off = C_e; p.Ct = C_e + C_u;
   p.rows = N * d * h * w;
   return p;
 }
@@ -363,5 +365,82 @@ extern "C" int pytc_upcat_deconv2_wgrad(const void* x_low, const void* dcat, flo
   hipLaunchKernelGGL(upcat_wgrad_reduce_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const float*)workspace, dw, db, S_used,
                      C_in, C_u);
   PYTC_LAUNCH_CHECK("upcat_deconv2_wgrad");
+  return PYTC_OK;
+}
+
+// ---- [up, skip] placement (MONAI UnetrUpBlock: torch.cat((transp_conv(inp), skip), 1)) and the plain k2/s2 deconv (C_e = 0:
+// UnetrPrUpBlock chains).  The same GEMMs with the up half at channel offset 0 and the skip after it; the grids are exactly twice the
+// low grid (no replicated faces).  The workspace of the weight gradient is sized by pytc_upcat_deconv2_wgrad_ws_elems.
+static int upfirst_check(const char* what, int N, int d, int h, int w, int C_in, int C_e, int C_u, int dtype) {
+  PYTC_REQUIRE(N >= 1 && d >= 1 && h >= 1 && w >= 1 && C_in >= 1 && C_e >= 0 && C_u >= 1, "%s: bad sizes", what);
+  PYTC_REQUIRE((long)N * 8 * d * h * w < (1L << 31), "%s: too many voxels for 32-bit voxel indices", what);
+  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  return PYTC_OK;
+}
+
+static UpcatParams upfirst_params(int N, int d, int h, int w, int C_in, int C_e, int C_u) {
+  UpcatParams p = upcat_params(N, d, h, w, 2 * d, 2 * h, 2 * w, C_in, C_e, C_u);
+  p.up_off = 0;
+  return p;
+}
+
+extern "C" int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* out, int N, int d,
+                                        int h, int wd, int C_in, int C_e, int C_u, int dtype, void* stream) {
+  if (int st = upfirst_check("deconv2_upfirst_fwd", N, d, h, wd, C_in, C_e, C_u, dtype)) return st;
+  PYTC_REQUIRE(x_low && w && out && (C_e == 0 || x_e), "deconv2_upfirst_fwd: null pointer");
+  UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
+  p.x_low = x_low; p.w = w; p.bias = bias; p.out = out;
+  hipStream_t st = (hipStream_t)stream;
+  const long vox = 8L * N * d * h * wd;
+  dim3 grid(ceil_div(8L * C_u, UP_BP), ceil_div(p.rows, UP_BQ));
+  if (dtype == PYTC_BF16) {
+    if (C_e) upcat_copy<bf16_t>(x_e, out, vox, C_e, C_e, 0, C_e + C_u, C_u, st);
+    hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_FWD>), grid, dim3(256), 0, st, p);
+  } else {
+    if (C_e) upcat_copy<float>(x_e, out, vox, C_e, C_e, 0, C_e + C_u, C_u, st);
+    hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_FWD>), grid, dim3(256), 0, st, p);
+  }
+  PYTC_LAUNCH_CHECK("deconv2_upfirst_fwd");
+  return PYTC_OK;
+}
+
+extern "C" int pytc_deconv2_upfirst_bwd_data(const void* dout, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd,
+                                             int C_in, int C_e, int C_u, int dtype, void* stream) {
+  if (int st = upfirst_check("deconv2_upfirst_bwd_data", N, d, h, wd, C_in, C_e, C_u, dtype)) return st;
+  PYTC_REQUIRE(dout && w, "deconv2_upfirst_bwd_data: null pointer");
+  UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
+  p.w = w; p.dcat = dout; p.out = dx_low;
+  hipStream_t st = (hipStream_t)stream;
+  const long vox = 8L * N * d * h * wd;
+  dim3 grid(ceil_div(C_in, UP_BP), ceil_div(p.rows, UP_BQ));
+  if (dtype == PYTC_BF16) {
+    if (dx_e && C_e) upcat_copy<bf16_t>(dout, dx_e, vox, C_e, C_e + C_u, C_u, C_e, 0, st);
+    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
+  } else {
+    if (dx_e && C_e) upcat_copy<float>(dout, dx_e, vox, C_e, C_e + C_u, C_u, C_e, 0, st);
+    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
+  }
+  PYTC_LAUNCH_CHECK("deconv2_upfirst_bwd_data");
+  return PYTC_OK;
+}
+
+extern "C" int pytc_deconv2_upfirst_wgrad(const void* x_low, const void* dout, float* workspace, float* dw, float* db, int N, int d, int h,
+                                          int wd, int C_in, int C_e, int C_u, int dtype, void* stream) {
+  if (int st = upfirst_check("deconv2_upfirst_wgrad", N, d, h, wd, C_in, C_e, C_u, dtype)) return st;
+  PYTC_REQUIRE(x_low && dout && workspace && dw, "deconv2_upfirst_wgrad: null pointer");
+  UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
+  p.x_low = x_low; p.dcat = dout; p.out = workspace;
+  const int ks = dtype == PYTC_BF16 ? Mma<bf16_t>::KSTEP : Mma<float>::KSTEP;
+  const int S = upcat_wgrad_splits(p.rows, C_in, C_u, ks);
+  p.rows_per_split = ceil_div(ceil_div(p.rows, S), ks) * ks;
+  const int S_used = ceil_div(p.rows, p.rows_per_split);
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid(ceil_div(C_in + 1, UP_BP), ceil_div(8L * C_u, UP_BQ), S_used);
+  if (dtype == PYTC_BF16) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
+  const long n = (long)C_in * 8 * C_u + C_u;
+  hipLaunchKernelGGL(upcat_wgrad_reduce_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const float*)workspace, dw, db, S_used,
+                     C_in, C_u);
+  PYTC_LAUNCH_CHECK("deconv2_upfirst_wgrad");
   return PYTC_OK;
 }

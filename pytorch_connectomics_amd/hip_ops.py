@@ -1914,3 +1914,204 @@ def conv3d_wgrad_strided(big: torch.Tensor, small: torch.Tensor, kernel, stride,
          _i3(stride), _i3(pad), dtype_code(big.dtype), _stream(),
          flops=2 * N * int(small.shape[1]) * int(small.shape[2]) * int(small.shape[3]) * ck * co * taps)
     return dW.view(kd, kh, kw, co, ck).permute(3, 4, 0, 1, 2).contiguous()
+
+
+# ---------------------------------------------------------------- MONAI UNETR ViT encoder (csrc/transformer_kernels.hip)
+def _rows2d(x: torch.Tensor, name: str):
+    _dev(x, name)
+    if x.dim() != 2:
+        raise ValueError(f"{name} must be a (rows, C) token matrix, got {tuple(x.shape)}")
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def linear_mfma_applies(x: torch.Tensor, c_in: int, c_out: int) -> bool:
+    """The bf16 token GEMMs run on the pointwise MFMA GEMM (pw_conv with row-major weights, csrc/pw_gemm_kernels.hip) wherever its
+    rules hold: bf16, C_in a multiple of 64, C_out a multiple of 128.  Everything else takes pytc_linear_* (FMA, any width, fp32)."""
+    return x.dtype == torch.bfloat16 and pw_conv_rowmajor_supported(c_in=c_in, c_out=c_out, in_dtype=torch.bfloat16,
+                                                                    out_dtype=torch.bfloat16)
+
+
+def _zeros_bias(n: int, device) -> torch.Tensor:
+    return torch.zeros((n,), dtype=torch.float32, device=device)        # the MFMA GEMM's accumulators start from a bias
+
+
+def linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None,
+               res: Optional[torch.Tensor] = None, x_gelu: bool = False) -> torch.Tensor:
+    """y = f(x) . W^T + bias + pos[row % P] + res on a (M, K) token matrix, f = GELU when x_gelu (x the stored pre-activation);
+    weight fp32 (N, K), bias fp32 (N), pos fp32 (P, N)."""
+    M, K = _rows2d(x, "x")
+    _dev(weight, "weight")
+    N = int(weight.shape[0])
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (N, K):
+        raise ValueError(f"linear_fwd: weight {tuple(weight.shape)} {weight.dtype} is not an fp32 ({N}, {K}) matrix")
+    if res is not None and (tuple(res.shape) != (M, N) or res.dtype != x.dtype):
+        raise ValueError(f"linear_fwd: residual {tuple(res.shape)} does not match ({M}, {N}) {x.dtype}")
+    if pos is None and linear_mfma_applies(x, K, N):
+        y = pw_conv(x, packed_rowmajor(weight), bias if bias is not None else _zeros_bias(N, x.device), N=1, rows_per_sample=M, c_in=K,
+                    c_out=N, out_dtype=torch.bfloat16, res=res, res_mode=nat.RES_ADD if res is not None else nat.RES_NONE,
+                    pre_act=nat.ACT_GELU if x_gelu else nat.ACT_NONE, w_paired=2)
+        return y.view(M, N)
+    P = int(pos.shape[0]) if pos is not None else 0
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    _run(f"linear_fwd[{K}->{N}]", _nbytes(x, weight, y, res), nat.lib().pytc_linear_fwd, _p(x), _p(weight), _p(bias), _p(pos), P,
+         _p(res), _p(y), M, N, K, int(bool(x_gelu)), dtype_code(x.dtype), _stream(), flops=2 * M * N * K, symbol="linear_gemm")
+    return y
+
+
+def linear_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, want_dx: bool = True, want_w: bool = True,
+               want_b: bool = False, pos_rows: int = 0, x_gelu: bool = False):
+    """Backward of linear_fwd -> (dx, dW fp32, db fp32, dpos fp32), each None when not wanted.  With x_gelu, x is the pre-activation:
+    dx = (dy . W) * gelu'(x) and dW = dy^T . gelu(x)."""
+    M, N = _rows2d(dy, "dy")
+    K = int(weight.shape[1])
+    dt = dtype_code(dy.dtype)
+    dx = dW = db = dpos = None
+    if want_dx:
+        if linear_mfma_applies(dy, N, K):
+            dx = pw_conv(dy, packed_rowmajor(weight, transposed=True), _zeros_bias(K, dy.device), N=1, rows_per_sample=M, c_in=N, c_out=K,
+                         out_dtype=torch.bfloat16, res=x if x_gelu else None,
+                         res_mode=nat.RES_GELU_BWD if x_gelu else nat.RES_NONE, w_paired=2).view(M, K)
+        else:
+            dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
+            _run(f"linear_bwd_data[{K}<-{N}]", _nbytes(dy, weight, dx), nat.lib().pytc_linear_bwd_data, _p(dy), _p(weight),
+                 _p(x) if x_gelu else None, _p(dx), M, N, K, dt, _stream(), flops=2 * M * N * K, symbol="linear_gemm")
+    if want_w and linear_mfma_applies(dy, K, N):
+        # the pointwise MFMA weight gradient (fixed-order slot reduction); it also gives the bias gradient
+        dW, db = pw_wgrad(x, dy, N=1, rows_per_sample=M, c_in=K, c_out=N, want_bias=want_b,
+                          x_act=nat.ACT_GELU if x_gelu else nat.ACT_NONE)
+        want_w = want_b = False
+    if want_w or want_b or pos_rows:
+        _dev(x, "x")
+        dW = torch.empty((N, K), dtype=torch.float32, device=dy.device) if want_w else dW
+        db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_b else db
+        dpos = torch.empty((pos_rows, N), dtype=torch.float32, device=dy.device) if pos_rows else None
+        _run(f"linear_wgrad[{K}x{N}]", _nbytes(dy, x, dW), nat.lib().pytc_linear_wgrad, _p(dy), _p(x), _p(dW if want_w else None),
+             _p(db if want_b else None), _p(dpos), int(pos_rows), M, N, K, int(bool(x_gelu)), dt, _stream(),
+             flops=2 * M * N * K if want_w else 0, symbol="linear_gemm")
+    return dx, dW, db, dpos
+
+
+def layernorm_wide(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
+    """nn.LayerNorm over the last axis of a (rows, C) matrix, C a multiple of 64 up to 1024; gamma / beta fp32 (C)."""
+    rows, C = _rows2d(x, "x")
+    y = torch.empty_like(x)
+    _run(f"layernorm_wide[{C}]", _nbytes(x, y), nat.lib().pytc_layernorm_wide, _p(x), _p(y), _p(gamma), _p(beta), rows, C, float(eps),
+         dtype_code(x.dtype), _stream())
+    return y
+
+
+def layernorm_wide_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, eps: float, want_params: bool = True):
+    """-> (dx, dgamma fp32, dbeta fp32); the parameter gradients are fixed-order sums (None when not wanted)."""
+    rows, C = _rows2d(x, "x")
+    _dev(dy, "dy")
+    dx = torch.empty_like(x)
+    slots = int(nat.lib().pytc_layernorm_wide_bwd_slots(rows))
+    part = torch.empty((slots, 2, C), dtype=torch.float32, device=x.device)
+    dg = torch.empty((C,), dtype=torch.float32, device=x.device) if want_params else None
+    db = torch.empty((C,), dtype=torch.float32, device=x.device) if want_params else None
+    _run(f"layernorm_wide_bwd[{C}]", _nbytes(dy, x, dx), nat.lib().pytc_layernorm_wide_bwd, _p(dy), _p(x), _p(gamma), _p(dx), _p(part),
+         _p(dg), _p(db), rows, C, float(eps), dtype_code(x.dtype), _stream())
+    return dx, dg, db
+
+
+def patch_gather16(x: torch.Tensor) -> torch.Tensor:
+    """Channels-last (B, D, H, W, C) -> (B * n_tok, 4096 C) rows of 16^3 patches in MONAI's (p1 p2 p3 c) order."""
+    _dev(x, "x")
+    B, D, H, W, C_ = (int(v) for v in x.shape)
+    out = torch.empty((B * (D // 16) * (H // 16) * (W // 16), 4096 * C_), dtype=x.dtype, device=x.device)
+    _run("patch_gather16", 2 * _nbytes(x), nat.lib().pytc_patch_gather16, _p(x), _p(out), B, D, H, W, C_, 0, dtype_code(x.dtype),
+         _stream())
+    return out
+
+
+def patch_scatter16(patches: torch.Tensor, shape) -> torch.Tensor:
+    """Inverse of patch_gather16: the (B, D, H, W, C) volume the patch rows came from."""
+    _dev(patches, "patches")
+    B, D, H, W, C_ = (int(v) for v in shape)
+    out = torch.empty((B, D, H, W, C_), dtype=patches.dtype, device=patches.device)
+    _run("patch_scatter16", 2 * _nbytes(patches), nat.lib().pytc_patch_gather16, _p(patches), _p(out), B, D, H, W, C_, 1,
+         dtype_code(patches.dtype), _stream())
+    return out
+
+
+def attention_supported(d_head: int) -> bool:
+    return bool(nat.lib().pytc_attention_supported(int(d_head)))
+
+
+def attention_fwd(qkv: torch.Tensor, B: int, heads: int, scale: float):
+    """Multi-head self-attention straight from the qkv GEMM output (B * N, 3 h), columns (qkv, head, d) -> (O (B * N, h) in
+    (head, d) order, lse fp32 (B, heads, N))."""
+    rows, C3 = _rows2d(qkv, "qkv")
+    N, hid = rows // B, C3 // 3
+    d = hid // heads
+    out = torch.empty((rows, hid), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+    _run(f"attention_fwd[N{N},d{d}]", _nbytes(qkv, out), nat.lib().pytc_attention_fwd, _p(qkv), _p(out), _p(lse), B, N, heads, d,
+         float(scale), dtype_code(qkv.dtype), _stream(), flops=4 * B * heads * N * N * d, symbol="attention_fwd")
+    return out, lse
+
+
+def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, B: int, heads: int, scale: float):
+    """-> dqkv (B * N, 3 h): dQ, dK, dV in the qkv column order, no atomics."""
+    rows, C3 = _rows2d(qkv, "qkv")
+    _dev(dout, "dout"), _dev(out, "out"), _dev(lse, "lse")
+    N, hid = rows // B, C3 // 3
+    d = hid // heads
+    dqkv = torch.empty_like(qkv)
+    dvec = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+    _run(f"attention_bwd[N{N},d{d}]", _nbytes(qkv, out, dout, dqkv), nat.lib().pytc_attention_bwd, _p(qkv), _p(out), _p(dout), _p(lse),
+         _p(dvec), _p(dqkv), B, N, heads, d, float(scale), dtype_code(qkv.dtype), _stream(), flops=12 * B * heads * N * N * d,
+         symbol="attention_bwd")
+    return dqkv
+
+
+def deconv2_upfirst_fwd(x_low: torch.Tensor, weight: torch.Tensor, x_e: Optional[torch.Tensor] = None,
+                        bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose3d(k 2, s 2, p 0) of channels-last x_low into channels [0, C_u) of a fresh (N, 2d, 2h, 2w, C_u + C_e) buffer, x_e
+    (same grid, C_e channels) copied behind it: torch.cat((up, skip), 1) of MONAI's UnetrUpBlock; x_e None is the plain deconv."""
+    _dev(x_low, "x_low"), _dev(weight, "weight")
+    N, d, h, w, C_in = (int(v) for v in x_low.shape)
+    C_u = int(weight.shape[1])
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (C_in, C_u, 2, 2, 2):
+        raise ValueError(f"deconv2_upfirst_fwd: weight {tuple(weight.shape)} is not an fp32 ({C_in}, C_u, 2, 2, 2) ConvTranspose3d weight")
+    C_e = 0
+    if x_e is not None:
+        _dev(x_e, "x_e")
+        if tuple(x_e.shape[:4]) != (N, 2 * d, 2 * h, 2 * w) or x_e.dtype != x_low.dtype:
+            raise ValueError(f"deconv2_upfirst_fwd: skip {tuple(x_e.shape)} {x_e.dtype} is not on the up-sampled grid of {tuple(x_low.shape)}")
+        C_e = int(x_e.shape[-1])
+    out = torch.empty((N, 2 * d, 2 * h, 2 * w, C_u + C_e), dtype=x_low.dtype, device=x_low.device)
+    rows = N * d * h * w
+    _run(f"deconv2_upfirst_fwd[{C_in}->{C_u}+{C_e}]", _nbytes(x_low, x_e, out, weight), nat.lib().pytc_deconv2_upfirst_fwd, _p(x_low),
+         _p(weight), _p(bias), _p(x_e), _p(out), N, d, h, w, C_in, C_e, C_u, dtype_code(x_low.dtype), _stream(),
+         flops=2 * rows * C_in * 8 * C_u, symbol="upcat_deconv2_fwd")
+    return out
+
+
+def deconv2_upfirst_bwd(dout: torch.Tensor, x_low: torch.Tensor, weight: torch.Tensor, C_e: int, want_dx_e: bool = True,
+                        want_dx_low: bool = True, want_w: bool = True, want_b: bool = False):
+    """Backward of deconv2_upfirst_fwd -> (dx_e, dx_low, dW fp32, db fp32), each None when not wanted."""
+    _dev(dout, "dout"), _dev(x_low, "x_low"), _dev(weight, "weight")
+    N, d, h, w, C_in = (int(v) for v in x_low.shape)
+    C_u = int(weight.shape[1])
+    if tuple(dout.shape) != (N, 2 * d, 2 * h, 2 * w, C_u + C_e) or dout.dtype != x_low.dtype:
+        raise ValueError(f"deconv2_upfirst_bwd: dout {tuple(dout.shape)} {dout.dtype} does not fit C_u = {C_u} + C_e = {C_e}")
+    dt = dtype_code(x_low.dtype)
+    rows = N * d * h * w
+    dx_e = torch.empty((*dout.shape[:4], C_e), dtype=dout.dtype, device=dout.device) if (want_dx_e and C_e) else None
+    dx_low = torch.empty_like(x_low) if want_dx_low else None
+    if dx_e is not None or dx_low is not None:
+        _run(f"deconv2_upfirst_bwd_data[{C_in}<-{C_u}+{C_e}]", _nbytes(dout, dx_e, dx_low, weight), nat.lib().pytc_deconv2_upfirst_bwd_data,
+             _p(dout), _p(weight), _p(dx_e), _p(dx_low), N, d, h, w, C_in, C_e, C_u, dt, _stream(),
+             flops=2 * rows * C_in * 8 * C_u if want_dx_low else 0, symbol="upcat_deconv2_bwd_data")
+    dW = db = None
+    if want_w or want_b:
+        ws = torch.empty((int(nat.lib().pytc_upcat_deconv2_wgrad_ws_elems(rows, C_in, C_u, dt)),), dtype=torch.float32, device=dout.device)
+        dW = torch.empty((C_in, C_u, 2, 2, 2), dtype=torch.float32, device=dout.device)
+        db = torch.empty((C_u,), dtype=torch.float32, device=dout.device) if want_b else None
+        _run(f"deconv2_upfirst_wgrad[{C_in}x{C_u}]", _nbytes(x_low, dout, ws, ws), nat.lib().pytc_deconv2_upfirst_wgrad, _p(x_low),
+             _p(dout), _p(ws), _p(dW), _p(db), N, d, h, w, C_in, C_e, C_u, dt, _stream(), flops=2 * rows * (C_in + 1) * 8 * C_u,
+             symbol="upcat_deconv2_wgrad")
+        if not want_w:
+            dW = None
+    return dx_e, dx_low, dW, db

@@ -5,6 +5,7 @@ from .registry import (get_architecture_builder, get_architecture_info, is_archi
 from . import mednext_models  # noqa: F401  (registers 'mednext', 'mednext_custom')
 from . import rsunet  # noqa: F401          (registers 'rsunet', 'rsunet_iso')
 from . import monai_models  # noqa: F401    (registers 'monai_unet', 'monai_basic_unet3d')
+from . import unetr  # noqa: F401           (registers 'monai_unetr')
 from .mednext_models import MedNeXtMultiHeadWrapper, MedNeXtTaskHead, MedNeXtWrapper
 
 
