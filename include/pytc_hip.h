@@ -860,6 +860,39 @@ int pytc_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int
                        void* stream);
 int pytc_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, int B, int N,
                        int heads, int d_head, float scale, int dtype, void* stream);
+/* ------------------------------------------------ MONAI SwinUNETR Swin encoder (csrc/swin_kernels.hip, csrc/transformer_kernels.hip) */
+/* Replaces the Swin transformer of the reference's `monai_swin_unetr` (monai_models.py:297-334 -> monai.networks.nets.SwinUNETR).
+ * geom (window geometry of one image) is a host array of 12 ints.
+ * pytc_window_attention_fwd / _bwd: softmax(Q K^T * scale + table[rel(i, j)][head] + mask) V per (window, head) on the qkv matrix of
+ *   nwin windows of N tokens (rows window-major), columns (qkv, head, d); d_head in {16, 32} (pytc_window_attention_supported).
+ *   geom = {windows per axis (3), window (3), padded grid (3), shift (3)}; rel is MONAI's 7^3 relative_position_index sliced to
+ *   [:N, :N]; mask = -100 between tokens of different compute_mask regions when any shift > 0.  table fp32 (2197, heads).  The
+ *   backward writes dqkv, and with dtable non-null the table gradient (2197, heads) through pytc_window_attention_bias_groups G
+ *   fixed-order window groups: partial holds G heads N N floats, dvec nwin heads N floats.  No atomics.
+ * pytc_window_partition: geom = {grid (3), window (3), padded grid (3), shift (3)}.  reverse 0: dst (B nW n, C) window rows of
+ *   src (B D H W, C) rolled by -shift on the zero-padded grid; reverse 1: dst (B D H W, C) = the window rows of src rolled back and
+ *   cropped, + res (same shape as dst, nullable).
+ * pytc_space_to_depth2: scatter 0: dst (B D/2 H/2 W/2, 8 C) = the 2^3 cells of src (B, D, H, W, C), slot-major columns; order 0 is the
+ *   Conv3d(k 2) tap order (kd, kh, kw), order 1 MONAI PatchMerging v1's x0..x7.  scatter 1: dst (B, D, H, W, C) = the fixed-order sum
+ *   of the slots that read each voxel (zero where none does).
+ * pytc_layernorm_any: LayerNorm over rows of C = 16 k <= 6144 channels, gamma / beta both null (no affine) or both given.
+ *   pytc_layernorm_any_bwd: dx; with dgamma non-null also dgamma / dbeta, using stats (2 rows floats) and partial (2 C
+ *   pytc_layernorm_any_bwd_slots(rows) floats). */
+int pytc_window_attention_supported(int d_head);
+int pytc_window_attention_bias_groups(int nwin, int N, int heads);
+int pytc_window_attention_fwd(const void* qkv, const float* table, const int* geom, void* out, float* lse, int nwin, int N, int heads,
+                              int d_head, float scale, int dtype, void* stream);
+int pytc_window_attention_bwd(const void* qkv, const float* table, const int* geom, const void* out, const void* dout, const float* lse,
+                              float* dvec, void* dqkv, float* partial, float* dtable, int nwin, int N, int heads, int d_head, float scale,
+                              int dtype, void* stream);
+int pytc_window_partition(const void* src, void* dst, const void* res, const int* geom, int B, int C, int reverse, int dtype,
+                          void* stream);
+int pytc_space_to_depth2(const void* src, void* dst, int B, int D, int H, int W, int C, int order, int scatter, int dtype, void* stream);
+int pytc_layernorm_any(const void* x, void* y, const float* gamma, const float* beta, int64_t rows, int C, float eps, int dtype,
+                       void* stream);
+int pytc_layernorm_any_bwd_slots(int64_t rows);
+int pytc_layernorm_any_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* stats, float* partial, float* dgamma,
+                           float* dbeta, int64_t rows, int C, float eps, int dtype, void* stream);
 int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* out, int N, int d, int h,
                              int wd, int C_in, int C_e, int C_u, int dtype, void* stream);
 int pytc_deconv2_upfirst_bwd_data(const void* dout, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd, int C_in,

@@ -289,6 +289,17 @@ _SIGS = {
     "pytc_deconv2_upfirst_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
     "pytc_deconv2_upfirst_bwd_data": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
     "pytc_deconv2_upfirst_wgrad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_void_p]),
+    "pytc_window_attention_supported": (C.c_int, [C.c_int]),
+    "pytc_window_attention_bias_groups": (C.c_int, [C.c_int] * 3),
+    "pytc_window_attention_fwd": (C.c_int, [C.c_void_p] * 2 + [C.POINTER(C.c_int32)] + [C.c_void_p] * 2 + [C.c_int] * 4
+                                  + [C.c_float, C.c_int, C.c_void_p]),
+    "pytc_window_attention_bwd": (C.c_int, [C.c_void_p] * 2 + [C.POINTER(C.c_int32)] + [C.c_void_p] * 7 + [C.c_int] * 4
+                                  + [C.c_float, C.c_int, C.c_void_p]),
+    "pytc_window_partition": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(C.c_int32)] + [C.c_int] * 4 + [C.c_void_p]),
+    "pytc_space_to_depth2": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 8 + [C.c_void_p]),
+    "pytc_layernorm_any": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "pytc_layernorm_any_bwd_slots": (C.c_int, [C.c_int64]),
+    "pytc_layernorm_any_bwd": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
 }
 
 _lib = None

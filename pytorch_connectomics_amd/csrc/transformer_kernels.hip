@@ -16,6 +16,9 @@
 //   forward : per query tile, loop over key tiles with an online softmax; O = acc / l, lse = m + log l saved for the backward.
 //   backward: Dv = rowsum(dO * O) (attn_bwd_dvec_kernel); dK, dV per KEY tile looping over query tiles (attn_bwd_dkv_kernel);
 //             dQ per QUERY tile looping over key tiles (attn_bwd_dq_kernel).  P is recomputed from Q, K and lse in both.
+//   WIN = true: MONAI SwinUNETR's shifted-window attention (pytc_window_attention_*): windows as the batch, the relative-position
+//             bias and shift mask added to every score (WinArgs), d = 16 / 32; the bias-table gradient is win_attn_dbias_kernel's
+//             fixed-slot per-window-group partials, summed in a fixed order by win_attn_table_grad_kernel.
 //
 // Linear layers: C[M][N] = sum_k A(m, k) B(k, n), one LDS-tiled FMA kernel with transposition flags for the three products
 // (Y = f(X) W^T, dX = dY W, dW = dY^T f(X)), f = GELU (erf form, pytc_common.h gelu_erf) applied to an operand as it is loaded
@@ -251,6 +254,47 @@ __global__ void patch_gather_kernel(const T* __restrict__ src, T* __restrict__ d
 // --------------------------------------------------------------------------------------------------------- attention
 constexpr int AT_T = 64;
 
+// Shifted-window attention of MONAI's SwinUNETR (WIN = true): the "batch" is the window, N = n tokens of it, and every score gets
+// S = q k^T * scale + table[rel(i, j)][head] (+ -100 where the shift-region labels of i and j differ).  rel(i, j) is MONAI's
+// relative_position_index of the FULL 7^3 window sliced to [:n, :n]: with i's coordinates taken in the 7^3 grid,
+// rel = c13(i) - c13(j) + 1098, c13(t) = (t / 49) * 169 + (t / 7 % 7) * 13 + t % 7.  The labels are compute_mask's, on the padded,
+// rolled grid: per axis 0 below P - ws, 1 below P - s, else 2 (every coordinate 2 when that axis' shift is 0).
+struct WinArgs {
+  const float* table;          // (2197, heads) fp32 relative-position bias table
+  int nw[3], ws[3], P[3], sh[3];  // windows per axis, window, padded grid, shift
+  int masked;                  // any shift > 0
+};
+
+__device__ __forceinline__ int win_axis_label(int p, int P, int ws, int s) { return s == 0 ? 2 : (p < P - ws ? 0 : (p < P - s ? 1 : 2)); }
+
+// c13[t] and label[t] of rows r0 + t (t < 64) of window `w` (global window index; w % windows-per-image locates it)
+__device__ __forceinline__ void win_meta(const WinArgs& wa, int w, int r0, int N, int* c13, int* lab) {
+  const int t = threadIdx.x;
+  if (t >= AT_T) return;
+  const int i = r0 + t;
+  if (i >= N) {
+    c13[t] = 0;
+    lab[t] = 0;
+    return;
+  }
+  c13[t] = (i / 49) * 169 + (i / 7 % 7) * 13 + i % 7;
+  int l = 0;
+  if (wa.masked) {
+    const int wl = w % (wa.nw[0] * wa.nw[1] * wa.nw[2]);
+    const int wd = wl / (wa.nw[1] * wa.nw[2]), wh = wl / wa.nw[2] % wa.nw[1], ww = wl % wa.nw[2];
+    const int id = i / (wa.ws[1] * wa.ws[2]), ih = i / wa.ws[2] % wa.ws[1], iw = i % wa.ws[2];
+    l = win_axis_label(wd * wa.ws[0] + id, wa.P[0], wa.ws[0], wa.sh[0]) * 9 +
+        win_axis_label(wh * wa.ws[1] + ih, wa.P[1], wa.ws[1], wa.sh[1]) * 3 + win_axis_label(ww * wa.ws[2] + iw, wa.P[2], wa.ws[2], wa.sh[2]);
+  }
+  lab[t] = l;
+}
+
+// the additive term of score (i, j): sm = {c13 q, label q, c13 k, label k} staged by win_meta
+__device__ __forceinline__ float win_add(const WinArgs& wa, const int* sm, int i, int j, int hd, int heads) {
+  const float b = wa.table[(sm[i] - sm[2 * AT_T + j] + 1098) * heads + hd];
+  return sm[AT_T + i] != sm[3 * AT_T + j] ? b - 100.f : b;
+}
+
 template <typename T, int D>
 __device__ __forceinline__ void attn_stage(float* s, const T* qkv, long row_stride, int col, int b, int N, int r0) {
   // s[i][c] (pitch D + 1) = qkv[(b * N + r0 + i) * row_stride + col + c], zero past N
@@ -294,21 +338,23 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
-// grid (ceil(N / 64), heads, B); dynamic LDS: Q, K, V (64 x (D + 1)) and P (64 x 65) floats
-template <typename T, int D>
+// grid (ceil(N / 64), heads, B); dynamic LDS: Q, K, V (64 x (D + 1)) and P (64 x 65) floats (+ 4 x 64 ints of window metadata)
+template <typename T, int D, bool WIN = false>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out, float* __restrict__ lse, int N,
-                                                       int heads, float scale) {
+                                                       int heads, float scale, WinArgs wa) {
   extern __shared__ float smem[];
   constexpr int CU = D / 16;
   float* sQ = smem;
   float* sK = sQ + AT_T * (D + 1);
   float* sV = sK + AT_T * (D + 1);
   float* sP = sV + AT_T * (D + 1);
+  int* sM = reinterpret_cast<int*>(sP + AT_T * (AT_T + 1));
   const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
   const int q0 = blockIdx.x * AT_T, hd = blockIdx.y, b = blockIdx.z;
   const int hid = heads * D;
   const long rs = 3L * hid;
   attn_stage<T, D>(sQ, qkv, rs, hd * D, b, N, q0);
+  if constexpr (WIN) win_meta(wa, b, q0, N, sM, sM + AT_T);
   float m[4], l[4], acc[4][CU];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -321,6 +367,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const T* __restrict__ qkv
     __syncthreads();
     attn_stage<T, D>(sK, qkv, rs, hid + hd * D, b, N, j0);
     attn_stage<T, D>(sV, qkv, rs, 2 * hid + hd * D, b, N, j0);
+    if constexpr (WIN) win_meta(wa, b, j0, N, sM + 2 * AT_T, sM + 3 * AT_T);
     __syncthreads();
     float S[4][4];
     attn_dot<D>(sQ, sK, S, ti, tj);
@@ -329,7 +376,9 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const T* __restrict__ qkv
       float mx = -INFINITY;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        S[r][s] = j0 + tj + 16 * s < N ? S[r][s] * scale : -INFINITY;
+        float sc = S[r][s] * scale;
+        if constexpr (WIN) sc += win_add(wa, sM, ti + 16 * r, tj + 16 * s, hd, heads);
+        S[r][s] = j0 + tj + 16 * s < N ? sc : -INFINITY;
         mx = fmaxf(mx, S[r][s]);
       }
       const float mn = fmaxf(m[r], row16_max(mx));     // finite: key j0 < N is in every tile
@@ -387,9 +436,10 @@ __global__ void attn_bwd_dvec_kernel(const T* __restrict__ dout, const T* __rest
 }
 
 // P and dS of one (query tile, key tile) pair into sP / sS ([query][key], pitch 65).  sX = Q rows, sY = K rows, sdO, sV as staged.
-template <int D>
+template <int D, bool WIN = false>
 __device__ __forceinline__ void attn_p_ds(const float* sQ, const float* sK, const float* sdO, const float* sV, const float* slse,
-                                          const float* sdv, float* sP, float* sS, int ti, int tj, int q0, int j0, int N, float scale) {
+                                          const float* sdv, float* sP, float* sS, int ti, int tj, int q0, int j0, int N, float scale,
+                                          const WinArgs& wa, const int* sM, int hd, int heads) {
   float S[4][4], dP[4][4];
   attn_dot<D>(sQ, sK, S, ti, tj);
   attn_dot<D>(sdO, sV, dP, ti, tj);
@@ -400,18 +450,20 @@ __device__ __forceinline__ void attn_p_ds(const float* sQ, const float* sK, cons
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int j = tj + 16 * s;
-      const float pv = (qok && j0 + j < N) ? expf(S[r][s] * scale - slse[i]) : 0.f;
+      float sc = S[r][s] * scale;
+      if constexpr (WIN) sc += win_add(wa, sM, i, j, hd, heads);
+      const float pv = (qok && j0 + j < N) ? expf(sc - slse[i]) : 0.f;
       sP[i * (AT_T + 1) + j] = pv;
       sS[i * (AT_T + 1) + j] = pv * (dP[r][s] - sdv[i]);
     }
   }
 }
 
-// grid (ceil(N / 64) key tiles, heads, B); LDS: K, V, Q, dO (64 x (D + 1)), P, dS (64 x 65), lse, dvec (64)
-template <typename T, int D>
+// grid (ceil(N / 64) key tiles, heads, B); LDS: K, V, Q, dO (64 x (D + 1)), P, dS (64 x 65), lse, dvec (64) (+ 4 x 64 window ints)
+template <typename T, int D, bool WIN = false>
 __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ dvec,
-                                                           T* __restrict__ dqkv, int N, int heads, float scale) {
+                                                           T* __restrict__ dqkv, int N, int heads, float scale, WinArgs wa) {
   extern __shared__ float smem[];
   constexpr int CU = D / 16, PD = AT_T * (D + 1), PP = AT_T * (AT_T + 1);
   float* sK = smem;
@@ -422,12 +474,14 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
   float* sS = sP + PP;
   float* slse = sS + PP;
   float* sdv = slse + AT_T;
+  int* sM = reinterpret_cast<int*>(sdv + AT_T);
   const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
   const int j0 = blockIdx.x * AT_T, hd = blockIdx.y, b = blockIdx.z;
   const int hid = heads * D;
   const long rs = 3L * hid;
   attn_stage<T, D>(sK, qkv, rs, hid + hd * D, b, N, j0);
   attn_stage<T, D>(sV, qkv, rs, 2 * hid + hd * D, b, N, j0);
+  if constexpr (WIN) win_meta(wa, b, j0, N, sM + 2 * AT_T, sM + 3 * AT_T);
   float dK[4][CU], dV[4][CU];       // keys ti + 16 r, channels tj + 16 u
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -442,8 +496,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
       slse[tid] = q0 + tid < N ? lse[sb + q0 + tid] : 0.f;
       sdv[tid] = q0 + tid < N ? dvec[sb + q0 + tid] : 0.f;
     }
+    if constexpr (WIN) win_meta(wa, b, q0, N, sM, sM + AT_T);
     __syncthreads();
-    attn_p_ds<D>(sQ, sK, sdO, sV, slse, sdv, sP, sS, ti, tj, q0, j0, N, scale);
+    attn_p_ds<D, WIN>(sQ, sK, sdO, sV, slse, sdv, sP, sS, ti, tj, q0, j0, N, scale, wa, sM, hd, heads);
     __syncthreads();
 #pragma unroll 4
     for (int i = 0; i < AT_T; ++i) {
@@ -479,10 +534,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const T* __restrict__
 }
 
 // grid (ceil(N / 64) query tiles, heads, B); LDS as attn_bwd_dkv_kernel
-template <typename T, int D>
+template <typename T, int D, bool WIN = false>
 __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                           const float* __restrict__ lse, const float* __restrict__ dvec,
-                                                          T* __restrict__ dqkv, int N, int heads, float scale) {
+                                                          T* __restrict__ dqkv, int N, int heads, float scale, WinArgs wa) {
   extern __shared__ float smem[];
   constexpr int CU = D / 16, PD = AT_T * (D + 1), PP = AT_T * (AT_T + 1);
   float* sK = smem;
@@ -493,6 +548,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
   float* sS = sP + PP;
   float* slse = sS + PP;
   float* sdv = slse + AT_T;
+  int* sM = reinterpret_cast<int*>(sdv + AT_T);
   const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
   const int q0 = blockIdx.x * AT_T, hd = blockIdx.y, b = blockIdx.z;
   const int hid = heads * D;
@@ -504,6 +560,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
     slse[tid] = q0 + tid < N ? lse[sb + q0 + tid] : 0.f;
     sdv[tid] = q0 + tid < N ? dvec[sb + q0 + tid] : 0.f;
   }
+  if constexpr (WIN) win_meta(wa, b, q0, N, sM, sM + AT_T);
   float dQ[4][CU];                  // queries ti + 16 r, channels tj + 16 u
 #pragma unroll
   for (int r = 0; r < 4; ++r)
@@ -513,8 +570,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
     __syncthreads();
     attn_stage<T, D>(sK, qkv, rs, hid + hd * D, b, N, j0);
     attn_stage<T, D>(sV, qkv, rs, 2 * hid + hd * D, b, N, j0);
+    if constexpr (WIN) win_meta(wa, b, j0, N, sM + 2 * AT_T, sM + 3 * AT_T);
     __syncthreads();
-    attn_p_ds<D>(sQ, sK, sdO, sV, slse, sdv, sP, sS, ti, tj, q0, j0, N, scale);
+    attn_p_ds<D, WIN>(sQ, sK, sdO, sV, slse, sdv, sP, sS, ti, tj, q0, j0, N, scale, wa, sM, hd, heads);
     __syncthreads();
 #pragma unroll 4
     for (int j = 0; j < AT_T; ++j) {
@@ -537,6 +595,83 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 #pragma unroll
     for (int u = 0; u < CU; ++u) row[hd * D + tj + 16 * u] = from_f32<T>(dQ[r][u] * scale);
   }
+}
+
+// Bias-table gradient, stage 1: partial[g][hd][i][j] = sum over windows w = g, g + G, g + 2 G, ... (in that order) of dS[w][hd][i][j],
+// dS = P (dP - dvec), P recomputed as in the backward kernels.  grid (ceil(N / 64) query tiles, ceil(N / 64) key tiles, heads * G);
+// LDS as attn_bwd_dkv_kernel.  Every partial element has one writer: no atomics.
+template <typename T, int D>
+__global__ void __launch_bounds__(256) win_attn_dbias_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+                                                             const float* __restrict__ lse, const float* __restrict__ dvec,
+                                                             float* __restrict__ partial, int nwin, int N, int heads, int G, float scale,
+                                                             WinArgs wa) {
+  extern __shared__ float smem[];
+  constexpr int PD = AT_T * (D + 1), PP = AT_T * (AT_T + 1);
+  float* sK = smem;
+  float* sV = sK + PD;
+  float* sQ = sV + PD;
+  float* sdO = sQ + PD;
+  float* sP = sdO + PD;
+  float* sS = sP + PP;
+  float* slse = sS + PP;
+  float* sdv = slse + AT_T;
+  int* sM = reinterpret_cast<int*>(sdv + AT_T);
+  const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+  const int q0 = blockIdx.x * AT_T, j0 = blockIdx.y * AT_T, hd = blockIdx.z % heads, g = blockIdx.z / heads;
+  const int hid = heads * D;
+  const long rs = 3L * hid;
+  float acc[4][4] = {};
+  for (int w = g; w < nwin; w += G) {
+    __syncthreads();
+    attn_stage<T, D>(sQ, qkv, rs, hd * D, w, N, q0);
+    attn_stage<T, D>(sdO, dout, hid, hd * D, w, N, q0);
+    attn_stage<T, D>(sK, qkv, rs, hid + hd * D, w, N, j0);
+    attn_stage<T, D>(sV, qkv, rs, 2 * hid + hd * D, w, N, j0);
+    const long sb = ((long)w * heads + hd) * N;
+    if (tid < AT_T) {
+      slse[tid] = q0 + tid < N ? lse[sb + q0 + tid] : 0.f;
+      sdv[tid] = q0 + tid < N ? dvec[sb + q0 + tid] : 0.f;
+    }
+    win_meta(wa, w, q0, N, sM, sM + AT_T);
+    win_meta(wa, w, j0, N, sM + 2 * AT_T, sM + 3 * AT_T);
+    __syncthreads();
+    attn_p_ds<D, true>(sQ, sK, sdO, sV, slse, sdv, sP, sS, ti, tj, q0, j0, N, scale, wa, sM, hd, heads);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[r][s] += sS[(ti + 16 * r) * (AT_T + 1) + tj + 16 * s];     // this thread's own writes
+  }
+  float* out = partial + ((long)g * heads + hd) * N * N;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = q0 + ti + 16 * r;
+    if (i >= N) continue;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int j = j0 + tj + 16 * s;
+      if (j < N) out[(long)i * N + j] = acc[r][s];
+    }
+  }
+}
+
+// Stage 2: dtable[r][hd] = sum over query rows i (ascending) of the key j with rel(i, j) = r, j < N, of sum_g partial[g][hd][i][j]
+// (g ascending).  rel is one-to-one in j for fixed i, so each (i, r) names at most one key.  One thread per table entry.
+__global__ void win_attn_table_grad_kernel(const float* __restrict__ partial, float* __restrict__ dtable, int N, int heads, int G) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= 2197 * heads) return;
+  const int r = e / heads, hd = e % heads;
+  const int od = r / 169 - 6, oh = r / 13 % 13 - 6, ow = r % 13 - 6;
+  const long plane = (long)heads * N * N;
+  float s = 0.f;
+  for (int i = 0; i < N; ++i) {
+    const int jd = i / 49 - od, jh = i / 7 % 7 - oh, jw = i % 7 - ow;
+    if (jd < 0 || jd > 6 || jh < 0 || jh > 6 || jw < 0 || jw > 6) continue;
+    const int j = jd * 49 + jh * 7 + jw;
+    if (j >= N) continue;
+    const float* p = partial + ((long)hd * N + i) * N + j;
+    for (int g = 0; g < G; ++g) s += p[g * plane];
+  }
+  dtable[e] = s;
 }
 
 }  // namespace pytc
@@ -683,7 +818,7 @@ static void attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N
   const void* k = reinterpret_cast<const void*>(&attn_fwd_kernel<T, D>);
   if (!ensure_dynamic_lds(k, lds, "attention_fwd")) return;
   hipLaunchKernelGGL((attn_fwd_kernel<T, D>), dim3(ceil_div(N, AT_T), heads, B), dim3(256), lds, st, (const T*)qkv, (T*)out, lse, N,
-                     heads, scale);
+                     heads, scale, WinArgs{});
 }
 
 extern "C" int pytc_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int heads, int d_head, float scale, int dtype,
@@ -714,9 +849,9 @@ static void attn_bwd_launch(const void* qkv, const void* out, const void* dout, 
   if (!ensure_dynamic_lds(kkv, lds, "attention_bwd") || !ensure_dynamic_lds(kq, lds, "attention_bwd")) return;
   dim3 grid(ceil_div(N, AT_T), heads, B);
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D>), grid, dim3(256), lds, st, (const T*)qkv, (const T*)dout, lse, (const float*)dvec,
-                     (T*)dqkv, N, heads, scale);
+                     (T*)dqkv, N, heads, scale, WinArgs{});
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D>), grid, dim3(256), lds, st, (const T*)qkv, (const T*)dout, lse, (const float*)dvec,
-                     (T*)dqkv, N, heads, scale);
+                     (T*)dqkv, N, heads, scale, WinArgs{});
 }
 
 extern "C" int pytc_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, int B,
@@ -732,5 +867,112 @@ extern "C" int pytc_attention_bwd(const void* qkv, const void* out, const void* 
     else attn_bwd_launch<float, 32>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
   }
   PYTC_LAUNCH_CHECK("attention_bwd");
+  return PYTC_OK;
+}
+
+// ------------------------------------------------------------------------------------------ shifted-window attention (Swin)
+extern "C" int pytc_window_attention_supported(int d_head) { return d_head == 16 || d_head == 32; }
+
+// G window groups of the bias-table gradient: enough (query tile, key tile, head, group) blocks to fill the GPU, at most nwin
+extern "C" int pytc_window_attention_bias_groups(int nwin, int N, int heads) {
+  const int tiles = ceil_div(N, AT_T) * ceil_div(N, AT_T) * std::max(heads, 1);
+  return std::max(1, std::min(nwin, ceil_div(2048, tiles)));
+}
+
+// geom = {windows per axis (3), window (3), padded grid (3), shift (3)} of one image; nwin = images * windows per image
+static int win_args(const char* what, const float* table, const int* geom, int nwin, int N, int heads, int d_head, int dtype,
+                    WinArgs* wa) {
+  PYTC_REQUIRE(table && geom && nwin >= 1 && heads >= 1, "%s: bad arguments", what);
+  PYTC_REQUIRE(pytc_window_attention_supported(d_head), "%s: head width %d has no kernel (16, 32)", what, d_head);
+  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  memset(wa, 0, sizeof(*wa));
+  wa->table = table;
+  int per_img = 1, n = 1;
+  for (int a = 0; a < 3; ++a) {
+    wa->nw[a] = geom[a]; wa->ws[a] = geom[3 + a]; wa->P[a] = geom[6 + a]; wa->sh[a] = geom[9 + a];
+    PYTC_REQUIRE(wa->ws[a] >= 1 && wa->ws[a] <= 7 && wa->nw[a] >= 1 && wa->nw[a] * wa->ws[a] == wa->P[a] && wa->sh[a] >= 0 &&
+                 wa->sh[a] < wa->ws[a], "%s: axis %d: %d windows of %d over a padded %d with shift %d is not a window grid", what, a,
+                 wa->nw[a], wa->ws[a], wa->P[a], wa->sh[a]);
+    per_img *= wa->nw[a];
+    n *= wa->ws[a];
+    wa->masked |= wa->sh[a] > 0;
+  }
+  PYTC_REQUIRE(n == N && nwin % per_img == 0, "%s: %d windows of %d tokens do not fit the geometry (%d-token windows, %d per image)",
+               what, nwin, N, n, per_img);
+  return PYTC_OK;
+}
+
+static size_t win_fwd_lds(int D) { return (3 * AT_T * (D + 1) + AT_T * (AT_T + 1) + 4 * AT_T) * sizeof(float); }
+static size_t win_bwd_lds(int D) { return (4 * AT_T * (D + 1) + 2 * AT_T * (AT_T + 1) + 2 * AT_T + 4 * AT_T) * sizeof(float); }
+
+template <typename T, int D>
+static void win_fwd_launch(const void* qkv, void* out, float* lse, int nwin, int N, int heads, float scale, const WinArgs& wa,
+                           hipStream_t st) {
+  const size_t lds = win_fwd_lds(D);
+  const void* k = reinterpret_cast<const void*>(&attn_fwd_kernel<T, D, true>);
+  if (!ensure_dynamic_lds(k, lds, "window_attention_fwd")) return;
+  hipLaunchKernelGGL((attn_fwd_kernel<T, D, true>), dim3(ceil_div(N, AT_T), heads, nwin), dim3(256), lds, st, (const T*)qkv, (T*)out,
+                     lse, N, heads, scale, wa);
+}
+
+extern "C" int pytc_window_attention_fwd(const void* qkv, const float* table, const int* geom, void* out, float* lse, int nwin, int N,
+                                         int heads, int d_head, float scale, int dtype, void* stream) {
+  WinArgs wa;
+  if (int s = win_args("window_attention_fwd", table, geom, nwin, N, heads, d_head, dtype, &wa)) return s;
+  PYTC_REQUIRE(qkv && out && lse, "window_attention_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PYTC_BF16) {
+    if (d_head == 16) win_fwd_launch<bf16_t, 16>(qkv, out, lse, nwin, N, heads, scale, wa, st);
+    else win_fwd_launch<bf16_t, 32>(qkv, out, lse, nwin, N, heads, scale, wa, st);
+  } else {
+    if (d_head == 16) win_fwd_launch<float, 16>(qkv, out, lse, nwin, N, heads, scale, wa, st);
+    else win_fwd_launch<float, 32>(qkv, out, lse, nwin, N, heads, scale, wa, st);
+  }
+  PYTC_LAUNCH_CHECK("window_attention_fwd");
+  return PYTC_OK;
+}
+
+template <typename T, int D>
+static void win_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* dvec, void* dqkv, float* partial,
+                           float* dtable, int nwin, int N, int heads, float scale, const WinArgs& wa, hipStream_t st) {
+  const size_t lds = win_bwd_lds(D);
+  const long rows = (long)nwin * heads * N;
+  hipLaunchKernelGGL(attn_bwd_dvec_kernel<T>, dim3(ceil_div(rows, 256)), dim3(256), 0, st, (const T*)dout, (const T*)out, dvec, nwin, N,
+                     heads, D);
+  const void* kkv = reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<T, D, true>);
+  const void* kq = reinterpret_cast<const void*>(&attn_bwd_dq_kernel<T, D, true>);
+  const void* kb = reinterpret_cast<const void*>(&win_attn_dbias_kernel<T, D>);
+  if (!ensure_dynamic_lds(kkv, lds, "window_attention_bwd") || !ensure_dynamic_lds(kq, lds, "window_attention_bwd") ||
+      !ensure_dynamic_lds(kb, lds, "window_attention_bwd"))
+    return;
+  dim3 grid(ceil_div(N, AT_T), heads, nwin);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, true>), grid, dim3(256), lds, st, (const T*)qkv, (const T*)dout, lse, (const float*)dvec,
+                     (T*)dqkv, N, heads, scale, wa);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, true>), grid, dim3(256), lds, st, (const T*)qkv, (const T*)dout, lse, (const float*)dvec,
+                     (T*)dqkv, N, heads, scale, wa);
+  if (dtable) {
+    const int G = pytc_window_attention_bias_groups(nwin, N, heads);
+    hipLaunchKernelGGL((win_attn_dbias_kernel<T, D>), dim3(ceil_div(N, AT_T), ceil_div(N, AT_T), heads * G), dim3(256), lds, st,
+                       (const T*)qkv, (const T*)dout, lse, (const float*)dvec, partial, nwin, N, heads, G, scale, wa);
+    hipLaunchKernelGGL(win_attn_table_grad_kernel, dim3(ceil_div(2197L * heads, 256)), dim3(256), 0, st, (const float*)partial, dtable, N,
+                       heads, G);
+  }
+}
+
+extern "C" int pytc_window_attention_bwd(const void* qkv, const float* table, const int* geom, const void* out, const void* dout,
+                                         const float* lse, float* dvec, void* dqkv, float* partial, float* dtable, int nwin, int N,
+                                         int heads, int d_head, float scale, int dtype, void* stream) {
+  WinArgs wa;
+  if (int s = win_args("window_attention_bwd", table, geom, nwin, N, heads, d_head, dtype, &wa)) return s;
+  PYTC_REQUIRE(qkv && out && dout && lse && dvec && dqkv && (!dtable || partial), "window_attention_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PYTC_BF16) {
+    if (d_head == 16) win_bwd_launch<bf16_t, 16>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
+    else win_bwd_launch<bf16_t, 32>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
+  } else {
+    if (d_head == 16) win_bwd_launch<float, 16>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
+    else win_bwd_launch<float, 32>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
+  }
+  PYTC_LAUNCH_CHECK("window_attention_bwd");
   return PYTC_OK;
 }

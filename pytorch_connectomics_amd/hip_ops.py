@@ -2065,6 +2065,128 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
     return dqkv
 
 
+# ---------------------------------------------------------------- MONAI SwinUNETR Swin encoder (csrc/swin_kernels.hip)
+def window_attention_supported(d_head: int) -> bool:
+    return bool(nat.lib().pytc_window_attention_supported(int(d_head)))
+
+
+def _i12(vals):
+    return (C.c_int32 * 12)(*[int(v) for v in vals])
+
+
+def window_attention_geom(grid, window, shift):
+    """The 12 ints of pytc_window_attention_*: windows per axis, window, zero-padded grid, shift."""
+    padded = [-(-int(g) // int(w)) * int(w) for g, w in zip(grid, window)]
+    return [p // int(w) for p, w in zip(padded, window)] + [int(w) for w in window] + padded + [int(s) for s in shift]
+
+
+def window_attention_fwd(qkv: torch.Tensor, table: torch.Tensor, geom, nwin: int, heads: int, scale: float):
+    """Swin window attention on the qkv matrix (nwin * n, 3 h) of window rows -> (O (nwin * n, h), lse fp32 (nwin, heads, n));
+    table fp32 (2197, heads), geom from window_attention_geom (the shift mask is on when any shift > 0)."""
+    rows, C3 = _rows2d(qkv, "qkv")
+    _dev(table, "table")
+    n, hid = rows // nwin, C3 // 3
+    d = hid // heads
+    out = torch.empty((rows, hid), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((nwin, heads, n), dtype=torch.float32, device=qkv.device)
+    _run(f"window_attention_fwd[n{n},d{d}]", _nbytes(qkv, out), nat.lib().pytc_window_attention_fwd, _p(qkv), _p(table), _i12(geom),
+         _p(out), _p(lse), nwin, n, heads, d, float(scale), dtype_code(qkv.dtype), _stream(), flops=4 * nwin * heads * n * n * d,
+         symbol="window_attention_fwd")
+    return out, lse
+
+
+def window_attention_bwd(qkv: torch.Tensor, table: torch.Tensor, geom, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor,
+                         nwin: int, heads: int, scale: float, want_table: bool = True):
+    """-> (dqkv (nwin * n, 3 h), dtable fp32 (2197, heads) or None); the table gradient is a fixed-order sum over the windows."""
+    rows, C3 = _rows2d(qkv, "qkv")
+    _dev(dout, "dout"), _dev(out, "out"), _dev(lse, "lse"), _dev(table, "table")
+    n, hid = rows // nwin, C3 // 3
+    d = hid // heads
+    dqkv = torch.empty_like(qkv)
+    dvec = torch.empty((nwin, heads, n), dtype=torch.float32, device=qkv.device)
+    dtable = part = None
+    if want_table:
+        G = int(nat.lib().pytc_window_attention_bias_groups(nwin, n, heads))
+        part = torch.empty((G, heads, n, n), dtype=torch.float32, device=qkv.device)
+        dtable = torch.empty((2197, heads), dtype=torch.float32, device=qkv.device)
+    _run(f"window_attention_bwd[n{n},d{d}]", _nbytes(qkv, out, dout, dqkv), nat.lib().pytc_window_attention_bwd, _p(qkv), _p(table),
+         _i12(geom), _p(out), _p(dout), _p(lse), _p(dvec), _p(dqkv), _p(part), _p(dtable), nwin, n, heads, d, float(scale),
+         dtype_code(qkv.dtype), _stream(), flops=(16 if want_table else 12) * nwin * heads * n * n * d, symbol="window_attention_bwd")
+    return dqkv, dtable
+
+
+def window_partition(x: torch.Tensor, B: int, grid, window, shift) -> torch.Tensor:
+    """Token matrix (B * D * H * W, C) -> window rows (B * nW * n, C): zero pad to whole windows, roll by -shift, partition."""
+    rows, C_ = _rows2d(x, "x")
+    g = window_attention_geom(grid, window, shift)
+    geom = list(grid) + g[3:6] + g[6:9] + g[9:12]
+    nrows = B * g[6] * g[7] * g[8]
+    out = torch.empty((nrows, C_), dtype=x.dtype, device=x.device)
+    _run("window_partition", _nbytes(x, out), nat.lib().pytc_window_partition, _p(x), _p(out), None, _i12(geom), B, C_, 0,
+         dtype_code(x.dtype), _stream())
+    return out
+
+
+def window_reverse(w: torch.Tensor, B: int, grid, window, shift, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverse of window_partition (roll back, crop) -> (B * D * H * W, C), + res when given (the block's residual)."""
+    _, C_ = _rows2d(w, "w")
+    g = window_attention_geom(grid, window, shift)
+    geom = list(grid) + g[3:6] + g[6:9] + g[9:12]
+    nrows = B * int(grid[0]) * int(grid[1]) * int(grid[2])
+    if res is not None and (tuple(res.shape) != (nrows, C_) or res.dtype != w.dtype):
+        raise ValueError(f"window_reverse: residual {tuple(res.shape)} {res.dtype} is not ({nrows}, {C_}) {w.dtype}")
+    out = torch.empty((nrows, C_), dtype=w.dtype, device=w.device)
+    _run("window_reverse", _nbytes(w, out, res), nat.lib().pytc_window_partition, _p(w), _p(out), _p(res), _i12(geom), B, C_, 1,
+         dtype_code(w.dtype), _stream())
+    return out
+
+
+def space_to_depth2(x: torch.Tensor, order: int) -> torch.Tensor:
+    """Channels-last (B, D, H, W, C) -> (B * D/2 * H/2 * W/2, 8 C): order 0 the Conv3d(k 2) tap order, 1 PatchMerging v1's x0..x7."""
+    _dev(x, "x")
+    B, D, H, W, C_ = (int(v) for v in x.shape)
+    out = torch.empty((B * (D // 2) * (H // 2) * (W // 2), 8 * C_), dtype=x.dtype, device=x.device)
+    _run("space_to_depth2", 2 * _nbytes(x), nat.lib().pytc_space_to_depth2, _p(x), _p(out), B, D, H, W, C_, int(order), 0,
+         dtype_code(x.dtype), _stream())
+    return out
+
+
+def space_to_depth2_bwd(cols: torch.Tensor, shape, order: int) -> torch.Tensor:
+    """Gradient of space_to_depth2: the (B, D, H, W, C) volume, each voxel the sum of the columns that read it."""
+    _dev(cols, "cols")
+    B, D, H, W, C_ = (int(v) for v in shape)
+    out = torch.empty((B, D, H, W, C_), dtype=cols.dtype, device=cols.device)
+    _run("space_to_depth2_bwd", 2 * _nbytes(cols), nat.lib().pytc_space_to_depth2, _p(cols), _p(out), B, D, H, W, C_, int(order), 1,
+         dtype_code(cols.dtype), _stream())
+    return out
+
+
+def layernorm_any(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float) -> torch.Tensor:
+    """LayerNorm over the last axis of a (rows, C) matrix, C a multiple of 16 up to 6144; gamma / beta fp32 (C), or both None."""
+    rows, C_ = _rows2d(x, "x")
+    y = torch.empty_like(x)
+    _run(f"layernorm_any[{C_}]", _nbytes(x, y), nat.lib().pytc_layernorm_any, _p(x), _p(y), _p(gamma), _p(beta), rows, C_, float(eps),
+         dtype_code(x.dtype), _stream())
+    return y
+
+
+def layernorm_any_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: Optional[torch.Tensor], eps: float, want_params: bool = True):
+    """-> (dx, dgamma fp32, dbeta fp32); the parameter gradients only with gamma and want_params (fixed-order sums)."""
+    rows, C_ = _rows2d(x, "x")
+    _dev(dy, "dy")
+    dx = torch.empty_like(x)
+    dg = db = stats = part = None
+    if gamma is not None and want_params:
+        slots = int(nat.lib().pytc_layernorm_any_bwd_slots(rows))
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        part = torch.empty((slots, 2, C_), dtype=torch.float32, device=x.device)
+        dg = torch.empty((C_,), dtype=torch.float32, device=x.device)
+        db = torch.empty((C_,), dtype=torch.float32, device=x.device)
+    _run(f"layernorm_any_bwd[{C_}]", _nbytes(dy, x, dx), nat.lib().pytc_layernorm_any_bwd, _p(dy), _p(x), _p(gamma), _p(dx), _p(stats),
+         _p(part), _p(dg), _p(db), rows, C_, float(eps), dtype_code(x.dtype), _stream())
+    return dx, dg, db
+
+
 def deconv2_upfirst_fwd(x_low: torch.Tensor, weight: torch.Tensor, x_e: Optional[torch.Tensor] = None,
                         bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ConvTranspose3d(k 2, s 2, p 0) of channels-last x_low into channels [0, C_u) of a fresh (N, 2d, 2h, 2w, C_u + C_e) buffer, x_e

@@ -1,4 +1,4 @@
-"""Architecture registry + the hot-path model builders (MedNeXt; RSUNet; MONAI-style residual U-Net)."""
+"""Architecture registry + the hot-path model builders (MedNeXt; RSUNet; MONAI-style U-Net, BasicUNet, UNETR and SwinUNETR)."""
 from .base import ConnectomicsModel
 from .registry import (get_architecture_builder, get_architecture_info, is_architecture_available,
                        list_architectures, register_architecture, unregister_architecture)
@@ -6,6 +6,7 @@ from . import mednext_models  # noqa: F401  (registers 'mednext', 'mednext_custo
 from . import rsunet  # noqa: F401          (registers 'rsunet', 'rsunet_iso')
 from . import monai_models  # noqa: F401    (registers 'monai_unet', 'monai_basic_unet3d')
 from . import unetr  # noqa: F401           (registers 'monai_unetr')
+from . import swin_unetr  # noqa: F401      (registers 'monai_swin_unetr')
 from .mednext_models import MedNeXtMultiHeadWrapper, MedNeXtTaskHead, MedNeXtWrapper
 
 

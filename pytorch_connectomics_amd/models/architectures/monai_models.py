@@ -397,13 +397,19 @@ class MONAIModelWrapper(ConnectomicsModel):
         from .unetr import UNETR, unetr_forward
         if isinstance(self.model, UNETR):
             return unetr_forward(self.model, x.contiguous()).float()
+        from .swin_unetr import SwinUNETR, swin_unetr_forward
+        if isinstance(self.model, SwinUNETR):
+            return swin_unetr_forward(self.model, x.contiguous()).float()
         return _run(self.model.model, x.contiguous()).float()
 
     @property
     def _arch(self) -> str:
+        from .swin_unetr import SwinUNETR
         from .unetr import UNETR
         if isinstance(self.model, UNETR):
             return "monai_unetr"
+        if isinstance(self.model, SwinUNETR):
+            return "monai_swin_unetr"
         return "monai_basic_unet3d" if isinstance(self.model, BasicUNet) else "monai_unet"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -411,7 +417,8 @@ class MONAIModelWrapper(ConnectomicsModel):
             raise RuntimeError(f"{self._arch} (pytorch_connectomics_amd) runs only on an MI355X/ROCm device: "
                                "there is no CPU path. Move the model and input to 'cuda'.")
         if x.dim() != 5:
-            name = {"monai_basic_unet3d": "BasicUNet", "monai_unetr": "UNETR"}.get(self._arch, "U-Net")
+            name = {"monai_basic_unet3d": "BasicUNet", "monai_unetr": "UNETR",
+                    "monai_swin_unetr": "SwinUNETR"}.get(self._arch, "U-Net")
             raise NotImplementedError(f"the MI355X engine runs the 3-D MONAI {name} on (B, C, D, H, W) inputs")
         y = self.forward_cl(to_channels_last(x.float()))
         return y.permute(0, 4, 1, 2, 3) if y.requires_grad else to_channels_first(y)
