@@ -26,8 +26,9 @@ extern "C" {
 /* 2 (round 5): pytc_mlp_args.per_sample (added in round 4 without a bump: ADVICE r04), pytc_dwconv3d_fwd with y = NULL, pytc_dwmix_*.
  * 4 (round 6): pytc_reduce_item.out_t (in the struct's former padding: a caller built against 3 may pass garbage there),
  * pytc_copy_zero_front, pytc_dwconv3d_bwd_data_add, pytc_pw_wgrad_groupnorm leaves the per-sample terms in the partials region at sps == 1.
+ * 5: pytc_cldice_* (the clDice soft skeleton and its gradient).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 4
+#define PYTC_ABI_VERSION 5
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -918,6 +919,28 @@ int pytc_grad_norm_multi(const void* table, const void* chunks, int n_chunks, fl
                          float* norm_coef, void* stream);
 int pytc_adamw_multi(const void* table, const void* chunks, int n_chunks, const float* groups_host, int n_groups,
                      const float* norm_coef, void* stream);
+
+/* Soft skeleton of the clDice topology loss (models/losses/losses.py:47-85, SoftClDiceLoss :456-721) on nvol fp32 volumes of
+ * D x H x W voxels (NCDHW, N C = nvol); is2d 1 for (N, C, H, W) inputs, passed with D = 1 (erosion over H and W only).
+ * pytc_cldice_erode: dst = the soft erosion of src (min of the three axis 3-min-pools, 2-D: two).  The caller fills
+ *   P = (n_iters + 1) levels of nvol D H W floats with p_1 .. p_{n+1}, p_{j+1} = erode(p_j), p_0 the probabilities.
+ * pytc_cldice_skeleton: skel (nullable) = the soft skeleton s_n, bit-identical to the reference's; with other non-null also
+ *   sums[2 vol + 0] = sum (s w)(other w), sums[2 vol + 1] = sum s w per volume (w = 1 when weight is null), from
+ *   partial (2 nvol pytc_cldice_tiles(D H W) floats) reduced in a fixed order.
+ * pytc_cldice_chain_bwd: given coef = {alpha (nvol), beta (nvol), gamma (nvol)} with dL/ds_n = (alpha (t w) + beta) w, writes
+ *   gdiff ((n_iters + 1) levels) = dL/d(p_j - dilate(p_{j+1})) and arg ((n_iters + 1) byte levels) = the first-max window code.
+ * pytc_cldice_sweep_bwd: one level of the reverse sweep, level = n_iters + 1 .. 0: a_out = dL/dp_level from gdiff, arg and
+ *   a_next = dL/dp_{level+1} (unused at level n_iters + 1); at level 0 plus gamma (skel_t w) w when skel_t is non-null.
+ *   Gradients are routed as torch autograd does on ties (first max in scan order, halves on minimum ties), in gather form. */
+int pytc_cldice_tiles(int64_t voxels);
+int pytc_cldice_erode(const float* src, float* dst, int nvol, int D, int H, int W, int is2d, void* stream);
+int pytc_cldice_skeleton(const float* p0, const float* P, float* skel, const float* other, const float* weight, float* partial,
+                         float* sums, int nvol, int D, int H, int W, int n_iters, int is2d, void* stream);
+int pytc_cldice_chain_bwd(const float* p0, const float* P, const float* target, const float* weight, const float* coef, float* gdiff,
+                          uint8_t* arg, int nvol, int D, int H, int W, int n_iters, int is2d, void* stream);
+int pytc_cldice_sweep_bwd(const float* p0, const float* P, const float* gdiff, const uint8_t* arg, const float* a_next, float* a_out,
+                          const float* skel_t, const float* weight, const float* coef, int nvol, int D, int H, int W, int n_iters,
+                          int level, int is2d, void* stream);
 
 #ifdef __cplusplus
 }

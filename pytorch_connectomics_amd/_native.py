@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 4          # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 5          # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -300,6 +300,11 @@ _SIGS = {
     "pytc_layernorm_any": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "pytc_layernorm_any_bwd_slots": (C.c_int, [C.c_int64]),
     "pytc_layernorm_any_bwd": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "pytc_cldice_tiles": (C.c_int, [C.c_int64]),
+    "pytc_cldice_erode": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
+    "pytc_cldice_skeleton": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
+    "pytc_cldice_chain_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
+    "pytc_cldice_sweep_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 7 + [C.c_void_p]),
 }
 
 _lib = None

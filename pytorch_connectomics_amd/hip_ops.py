@@ -2237,3 +2237,82 @@ def deconv2_upfirst_bwd(dout: torch.Tensor, x_low: torch.Tensor, weight: torch.T
         if not want_w:
             dW = None
     return dx_e, dx_low, dW, db
+
+
+# ---- clDice soft skeleton (csrc/cldice_kernels.hip) -----------------------------------------------------------------------------
+def _cldice_geo(x: torch.Tensor, name: str):
+    """(nvol, D, H, W, is2d) of a contiguous fp32 (N, C, D, H, W) or (N, C, H, W) volume."""
+    _dev(x, name)
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: the clDice kernels take float32, got {x.dtype}")
+    if x.dim() == 5:
+        N, C_, D, H, W = (int(v) for v in x.shape)
+        return N * C_, D, H, W, 0
+    if x.dim() == 4:
+        N, C_, H, W = (int(v) for v in x.shape)
+        return N * C_, 1, H, W, 1
+    raise ValueError(f"{name}: expected a 4-D or 5-D tensor, got shape {tuple(x.shape)}")
+
+
+def cldice_levels(prob: torch.Tensor, num_iters: int) -> torch.Tensor:
+    """(num_iters + 1, *prob.shape): p_1 .. p_{n+1}, each the soft erosion of the one before (p_0 = prob)."""
+    nvol, D, H, W, is2d = _cldice_geo(prob, "prob")
+    n = int(num_iters)
+    if n < 0:
+        raise ValueError(f"num_iters must be >= 0, got {n}")
+    P = torch.empty((n + 1, *prob.shape), dtype=prob.dtype, device=prob.device)
+    src = prob
+    for j in range(n + 1):
+        _run("cldice_erode", 2 * _nbytes(prob), nat.lib().pytc_cldice_erode, _p(src), _p(P[j]), nvol, D, H, W, is2d, _stream())
+        src = P[j]
+    return P
+
+
+def cldice_skeleton(prob: torch.Tensor, P: torch.Tensor, num_iters: int, other: Optional[torch.Tensor] = None,
+                    weight: Optional[torch.Tensor] = None, want_skeleton: bool = True):
+    """-> (skeleton or None, sums or None): the soft skeleton of `prob` from its eroded levels P, and with `other` the per-volume
+    sums (N, C, 2) = (sum (s w)(other w), sum s w), w = weight or 1, reduced in a fixed order."""
+    nvol, D, H, W, is2d = _cldice_geo(prob, "prob")
+    _dev(P, "P")
+    for t, nm in ((other, "other"), (weight, "weight")):
+        if t is not None and (_dev(t, nm).shape != prob.shape or t.dtype != torch.float32):
+            raise ValueError(f"{nm} must be float32 of shape {tuple(prob.shape)}, got {t.dtype} {tuple(t.shape)}")
+    skel = torch.empty_like(prob) if want_skeleton else None
+    sums = part = None
+    if other is not None:
+        sums = torch.empty((nvol, 2), dtype=torch.float32, device=prob.device)
+        part = torch.empty((nvol * nat.lib().pytc_cldice_tiles(D * H * W) * 2,), dtype=torch.float32, device=prob.device)
+    _run(f"cldice_skeleton[n={int(num_iters)}]", _nbytes(prob, P, skel, other, weight), nat.lib().pytc_cldice_skeleton, _p(prob), _p(P),
+         _p(skel), _p(other), _p(weight), _p(part), _p(sums), nvol, D, H, W, int(num_iters), is2d, _stream())
+    return skel, (sums.view(*prob.shape[:2], 2) if sums is not None else None)
+
+
+def soft_skeleton(prob: torch.Tensor, num_iters: int) -> torch.Tensor:
+    """The reference's `_soft_skeletonize_pool(prob, num_iters)` (models/losses/losses.py:74-85) on HIP, bit-identical in fp32:
+    prob is (N, C, D, H, W) or (N, C, H, W)."""
+    prob = prob.contiguous()
+    return cldice_skeleton(prob, cldice_levels(prob, num_iters), num_iters)[0]
+
+
+def cldice_backward(prob: torch.Tensor, P: torch.Tensor, num_iters: int, target: torch.Tensor, weight: Optional[torch.Tensor],
+                    coef: torch.Tensor, skel_t: Optional[torch.Tensor]) -> torch.Tensor:
+    """dL/dprob for L with dL/ds_n = (alpha (target w) + beta) w and a direct term gamma (skel_t w) w; coef (3, N, C) = alpha, beta,
+    gamma per volume (device values: no host synchronisation)."""
+    nvol, D, H, W, is2d = _cldice_geo(prob, "prob")
+    n = int(num_iters)
+    _dev(P, "P")
+    _dev(target, "target")
+    coef = _dev(coef.to(torch.float32).contiguous(), "coef")
+    if coef.numel() != 3 * nvol:
+        raise ValueError(f"coef must hold 3 x {nvol} values, got {coef.numel()}")
+    gdiff = torch.empty((n + 1, *prob.shape), dtype=torch.float32, device=prob.device)
+    arg = torch.empty((n + 1, *prob.shape), dtype=torch.uint8, device=prob.device)
+    lib = nat.lib()
+    _run(f"cldice_chain_bwd[n={n}]", _nbytes(prob, P, target, weight, gdiff, arg), lib.pytc_cldice_chain_bwd, _p(prob), _p(P),
+         _p(target), _p(weight), _p(coef), _p(gdiff), _p(arg), nvol, D, H, W, n, is2d, _stream())
+    a_next, a_out = torch.empty_like(prob), torch.empty_like(prob)
+    for j in range(n + 1, -1, -1):
+        _run("cldice_sweep_bwd", 4 * _nbytes(prob), lib.pytc_cldice_sweep_bwd, _p(prob), _p(P), _p(gdiff), _p(arg),
+             _p(a_next) if j <= n else None, _p(a_out), _p(skel_t), _p(weight), _p(coef), nvol, D, H, W, n, j, is2d, _stream())
+        a_next, a_out = a_out, a_next
+    return a_next
