@@ -27,8 +27,9 @@ extern "C" {
  * 4 (round 6): pytc_reduce_item.out_t (in the struct's former padding: a caller built against 3 may pass garbage there),
  * pytc_copy_zero_front, pytc_dwconv3d_bwd_data_add, pytc_pw_wgrad_groupnorm leaves the per-sample terms in the partials region at sps == 1.
  * 5: pytc_cldice_* (the clDice soft skeleton and its gradient).
+ * 6: the key set of pytc_set_tuning is closed: an unknown key returns PYTC_ERR_INVALID (the last error names it).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 5
+#define PYTC_ABI_VERSION 6
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -78,7 +79,8 @@ int pytc_abi_version(void);
 const char* pytc_last_error(void);
 /* fills cu_count / lds_bytes_per_cu / gcn arch name of `device`; returns status */
 int pytc_device_info(int device, int* cu_count, int* lds_bytes_per_cu, char* arch, int arch_len);
-/* integer tuning knobs (kernel-variant selection for A/B measurements; defaults are the tuned ones) */
+/* integer tuning knobs (kernel-variant selection for A/B parity tests; defaults are the tuned ones).  The accepted keys, their defaults
+ * and meanings are the rows of PYTC_KNOBS in pytorch_connectomics_amd/csrc/pytc_common.h; any other key returns PYTC_ERR_INVALID */
 int pytc_set_tuning(const char* key, int value);
 
 /* ---------------------------------------------------------------- sliding window --------- */

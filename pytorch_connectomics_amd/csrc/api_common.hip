@@ -57,24 +57,26 @@ static bool ensure_dynamic_lds_impl(const void* kernel, size_t bytes, const char
 }  // namespace pytc
 
 namespace pytc {
-// Small registry of integer tuning knobs (kernel variant selection for A/B measurements).
-static struct { char key[48]; int value; } g_knobs[64];
-static int g_nknobs = 0;
-int tuning_get(const char* key, int dflt) {
-  for (int i = 0; i < g_nknobs; ++i)
-    if (!strcmp(g_knobs[i].key, key)) return g_knobs[i].value;
-  return dflt;
-}
+// The knob table of pytc_common.h (PYTC_KNOBS): names, and the current values (process-global, set before the launches they steer).
+static const char* const g_knob_names[K_COUNT] = {
+#define PYTC_KNOB_NAME(name, dflt, doc) #name,
+    PYTC_KNOBS(PYTC_KNOB_NAME)
+#undef PYTC_KNOB_NAME
+};
+static int g_knob_values[K_COUNT] = {
+#define PYTC_KNOB_DEFAULT(name, dflt, doc) dflt,
+    PYTC_KNOBS(PYTC_KNOB_DEFAULT)
+#undef PYTC_KNOB_DEFAULT
+};
+int tuning_get(Knob k) { return g_knob_values[k]; }
 }  // namespace pytc
 
 extern "C" int pytc_set_tuning(const char* key, int value) {
-  if (!key || strlen(key) >= 48) return PYTC_ERR_INVALID;
-  for (int i = 0; i < pytc::g_nknobs; ++i)
-    if (!strcmp(pytc::g_knobs[i].key, key)) { pytc::g_knobs[i].value = value; return PYTC_OK; }
-  if (pytc::g_nknobs >= 64) return PYTC_ERR_INVALID;
-  strcpy(pytc::g_knobs[pytc::g_nknobs].key, key);
-  pytc::g_knobs[pytc::g_nknobs++].value = value;
-  return PYTC_OK;
+  PYTC_REQUIRE(key, "set_tuning: null key");
+  for (int i = 0; i < pytc::K_COUNT; ++i)
+    if (!strcmp(pytc::g_knob_names[i], key)) { pytc::g_knob_values[i] = value; return PYTC_OK; }
+  pytc::set_error("set_tuning: unknown knob '%.64s' (the accepted keys are the rows of PYTC_KNOBS in csrc/pytc_common.h)", key);
+  return PYTC_ERR_INVALID;
 }
 
 extern "C" int pytc_abi_version(void) { return PYTC_ABI_VERSION; }

@@ -277,7 +277,7 @@ bool conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const
                          int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
                          int dtype, hipStream_t s) {
   if (C_in != 1 || kd != 3 || kh != 3 || kw != 3 || pad != 1 || (stride != 1 && stride != 2) || ab || act_in != PYTC_ACT_NONE ||
-      e.res_mode != PYTC_RES_NONE || tuning_get("conv_c1_stencil", 1) == 0)
+      e.res_mode != PYTC_RES_NONE)
     return false;
   if (stride == 1 && (Do != Di || Ho != Hi || Wo != Wi)) return false;
   if (stride == 2 && (Do != (Di + 1) / 2 || Ho != (Hi + 1) / 2 || Wo != (Wi + 1) / 2)) return false;
@@ -305,7 +305,7 @@ constexpr int CT_TZ = 4, CT_TY = 8, CT_TX = 16;
 struct ConvTile { int KC, nchunks, G, tzh, tyh, txh, tiles_z, tiles_y, tiles_x; int lds_total; };     // lds_total: dynamic LDS bytes of the launch
 // the eight phases of a stride-2 transposed gather in ONE launch (blockIdx.z = phase = 4a + 2b + c): per phase the tap extents are
 // (1 + a, 1 + b, 1 + c), the groups per chunk G and the element offset of its weight image differ; n = 0: an ordinary conv
-struct ConvPhases { int n; int probe; };      // probe (measurements only, wrong results): 1 = no matrix loop, 2 = no staging loads, 3 = no epilogue
+struct ConvPhases { int n; int probe; };      // probe: every launch passes 0 (1 = no matrix loop, 2 = no staging loads, 3 = no epilogue)
 
 // channels per staged chunk: the whole (narrow) layer when it fits one chunk, else the widest divisor among 32 / 16 / 8
 static __host__ __device__ inline int conv_kc(int C_in) {
@@ -469,7 +469,7 @@ conv3d_tile_kernel(ConvParams p, ConvTile t, ConvPhases ps) {
     constexpr int AD = MT == 1 ? 6 : (MT == 2 ? 4 : 1);
     // ... and (MT <= 2) the B fragments of the NEXT group are read from LDS while the matrix instructions of the current one run: the
     // small launches put ONE wave on a SIMD, so the koff -> address -> ds_read_b128 chain of a group (two LDS round trips) was paid in
-    // full 216 times per wave (matrix loop of 256 -> 256: 80 us for 12 us of matrix instructions, tools/r06_conv_tile_probe.py).  Buffer
+    // full 216 times per wave (matrix loop of 256 -> 256: 80 us for 12 us of matrix instructions).  Buffer
     // parity is the ring slot's (AD is even).
     constexpr bool BDB = MT <= 2;
     bf16x8_t ring[AD][MT];
@@ -529,7 +529,7 @@ conv3d_tile_kernel(ConvParams p, ConvTile t, ConvPhases ps) {
   const int x = x0 + r;
   // Round 6 (second session): the results turn round in LDS before they are stored.  A lane ends
   // with 4 channels of one voxel -- 8-byte stores 2 * C_out bytes apart: at 24 -> 24 k133 on 2 x 18 x 256 x 256 (RSUNet's stock
-  // full-resolution layer) the epilogue was 93 of the launch's 183 us (probe 3 of tools/r06_conv_tile_probe.py) for 113 MB of output.
+  // full-resolution layer) the epilogue was 93 of the launch's 183 us (measured without it) for 113 MB of output.
   // Each wave writes its z plane's (bias + activation)-finished fp32 values into a wave-private [y][x][channel] image (row pitch
   // CW + 4 floats: the 16 x positions of a float4 column fall on 16 distinct bank groups) over the input tile, which every wave is done
   // with, and reads whole voxel rows back: a lane takes 8 consecutive channels, adds the residual's 16 bytes, rounds ONCE and stores 16
@@ -750,14 +750,10 @@ static void launch_conv_tile_mt(const ConvParams& p, const ConvTile& t, size_t l
   ConvTile tt = t;
   // narrow layers turn their results round in LDS (the kernel's epilogue): room for the waves' fp32 [8][16][MT * 16 + 4] images
   size_t total = lds_bytes;
-  const int knob = tuning_get("conv_tile_lds_epilogue", 3);      // bit 0: MT <= 2, bit 1: MT = 4 (two passes)
-  const bool on = MT <= 2 ? (knob & 1) != 0 : (knob & 2) != 0;
-  if (on) {
-    const size_t need = (size_t)4 * CT_TY * 16 * ((MT >= 2 ? 32 : 16) + 4) * 4;
-    if (need <= 80 * 1024 && need > total) total = need;
-  }
-  tt.lds_total = on ? (int)total : 0;
-  hipLaunchKernelGGL((conv3d_tile_kernel<MT>), grid, dim3(256), total, s, p, tt, ConvPhases{0, tuning_get("conv_tile_probe", 0)});
+  const size_t need = (size_t)4 * CT_TY * 16 * ((MT >= 2 ? 32 : 16) + 4) * 4;      // (MT = 4 takes two passes)
+  if (need <= 80 * 1024 && need > total) total = need;
+  tt.lds_total = (int)total;
+  hipLaunchKernelGGL((conv3d_tile_kernel<MT>), grid, dim3(256), total, s, p, tt, ConvPhases{0, 0});
 }
 
 template <int MT>
@@ -772,8 +768,7 @@ static void launch_conv_tile(const ConvParams& p, ConvTile t, size_t lds_bytes, 
   // deep levels (2 x 18 x 20 x 20 voxels = 60 spatial tiles): 64 output channels per workgroup leave 120 workgroups for 256 CUs;
   // fewer output tiles per workgroup (every workgroup stages the same input tile: L2 hits) until one per CU exists (more costs level 1 its 64-channel reuse: 40 -> 55 us)
   const long spatial = (long)p.N * t.tiles_z * t.tiles_y * t.tiles_x;
-  if (tuning_get("conv_tile_small_mt", 1))
-    while (MT > 1 && spatial * ((p.MTt + MT - 1) / MT) < 256) MT >>= 1;
+  while (MT > 1 && spatial * ((p.MTt + MT - 1) / MT) < 256) MT >>= 1;
   dim3 grid((unsigned)spatial, (unsigned)((p.MTt + MT - 1) / MT));
   switch (MT) {
     case 1: launch_conv_tile_mt<1>(p, t, lds_bytes, grid, s); break;
@@ -787,7 +782,7 @@ static void launch_conv(const ConvParams& p, hipStream_t s) {
   constexpr int NT = 4;
   const long rps = (long)p.D * p.H * p.W;
   const size_t thin_lds = (size_t)p.kd * p.kh * p.kw * p.C_in * 16 * sizeof(float);
-  if (p.C_in <= 4 && thin_lds <= 48 * 1024 && tuning_get("conv_thin_in", 1) != 0) {
+  if (p.C_in <= 4 && thin_lds <= 48 * 1024) {
     dim3 grid((unsigned)((rps + 255) / 256), (unsigned)p.MTt, (unsigned)p.N);
     hipLaunchKernelGGL((conv3d_thin_in_kernel<TI, TW, TO>), grid, dim3(256), thin_lds, s, p);
     return;
@@ -941,7 +936,7 @@ extern "C" int pytc_convT3d_phase_plan(int C_out, int C_in, int dtype, int64_t* 
 
 extern "C" int pytc_convT3d_phase_supported(int C_out, int C_in, int dtype) {
   ConvTile t[8]; size_t lds[8];
-  return (C_out >= 1 && C_in >= 1 && convT_phase_plan(dtype, C_in, t, lds) && tuning_get("convT_phase_tile", 1) != 0) ? 1 : 0;
+  return (C_out >= 1 && C_in >= 1 && convT_phase_plan(dtype, C_in, t, lds)) ? 1 : 0;
 }
 
 /* a->D/H/W: the OUTPUT grid (= 2 x in_dims), a->w_packed: the eight phase images (pytc_convT3d_phase_plan offsets), a->kd = kh = kw = 3 */

@@ -800,7 +800,7 @@ struct SwMfmaPlan { bool ok; int mt, nt, tiles, slots; long per_slot; };
 static SwMfmaPlan sw_mfma_plan(int N, const int32_t* small_dims, int C_k, int C_o, const int32_t* kernel, const int32_t* stride,
                                const int32_t* pad, int dtype) {
   SwMfmaPlan p{};
-  p.ok = dtype == PYTC_BF16 && C_k % 16 == 0 && C_o % 16 == 0 && tuning_get("conv_wgrad_s2_mfma", 1) != 0;
+  p.ok = dtype == PYTC_BF16 && C_k % 16 == 0 && C_o % 16 == 0;
   for (int a = 0; a < 3 && p.ok; ++a) p.ok = kernel[a] == 3 && (!stride || stride[a] == 2) && (!pad || pad[a] == 1);
   if (!p.ok) return p;
   p.mt = C_o % 32 == 0 ? 2 : 1;
@@ -830,7 +830,7 @@ using namespace pytc;
 
 // the line-reduction kernel: one input channel, 32 or 64 gradient channels, k 3 / stride 2 / pad 1 on every axis, lines that fit 64 KB of LDS
 static bool sw_c1_line_ok(const SwGeom& g, int C_k, int C_o, int dtype) {
-  if (C_k != 1 || (C_o != 32 && C_o != 64) || (dtype != PYTC_BF16 && dtype != PYTC_F32) || tuning_get("conv3d_wgrad_c1_line", 1) == 0) return false;
+  if (C_k != 1 || (C_o != 32 && C_o != 64) || (dtype != PYTC_BF16 && dtype != PYTC_F32)) return false;
   if (g.kd != 3 || g.kh != 3 || g.kw != 3 || g.sd != 2 || g.sh != 2 || g.sw != 2 || g.pd != 1 || g.ph != 1 || g.pw != 1) return false;
   return (size_t)(9 * (g.Wb + 2) + g.Ws * C_o) * sizeof(float) <= 64 * 1024 && 2 * (g.Ws - 1) + 2 - 1 < g.Wb + 1;
 }
@@ -878,8 +878,7 @@ extern "C" int pytc_conv3d_strided_fwd(const pytc_conv3d_args* a, const int32_t*
   p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
   p.pd = pad[0]; p.ph = pad[1]; p.pw = pad[2];
   p.transposed = transposed ? 1 : 0;
-  p.phase_major = (p.transposed && p.sd == 2 && p.sh == 2 && p.sw == 2 && p.Do == 2 * p.Di && p.Ho == 2 * p.Hi && p.Wo == 2 * p.Wi &&
-                   tuning_get("convT_phase_major", 1) != 0) ? 1 : 0;
+  p.phase_major = (p.transposed && p.sd == 2 && p.sh == 2 && p.sw == 2 && p.Do == 2 * p.Di && p.Ho == 2 * p.Hi && p.Wo == 2 * p.Wi) ? 1 : 0;
   p.act_in = a->act_in; p.act_param = a->act_param;
   p.e.res = a->res; p.e.res_low = nullptr; p.e.res_bias = nullptr; p.e.y = a->y;
   p.e.rps_out = (long)a->D * a->H * a->W; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode; p.e.nt = 0;
@@ -943,8 +942,7 @@ extern "C" int pytc_conv3d_wgrad_strided(const void* big, const void* small, flo
     if (dtype == PYTC_BF16) { if (C_o == 32) SW_C1(bf16_t, 1); else SW_C1(bf16_t, 2); }
     else { if (C_o == 32) SW_C1(float, 1); else SW_C1(float, 2); }
 #undef SW_C1
-  } else if (C_k == 1 && g.kd == 3 && g.kh == 3 && g.kw == 3 && (dtype == PYTC_BF16 || dtype == PYTC_F32) &&
-      tuning_get("conv3d_wgrad_thin", 1) != 0) {
+  } else if (C_k == 1 && g.kd == 3 && g.kh == 3 && g.kw == 3 && (dtype == PYTC_BF16 || dtype == PYTC_F32)) {
     dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO);
     if (dtype == PYTC_BF16)
       hipLaunchKernelGGL(conv3d_wgrad_strided_thin1_kernel<bf16_t>, tgrid, block, 0, s, (const bf16_t*)big, (const bf16_t*)small,
@@ -952,7 +950,7 @@ extern "C" int pytc_conv3d_wgrad_strided(const void* big, const void* small, flo
     else
       hipLaunchKernelGGL(conv3d_wgrad_strided_thin1_kernel<float>, tgrid, block, 0, s, (const float*)big, (const float*)small,
                          workspace, rows_total, g, C_o, rps, slots);
-  } else if (C_k <= SWT_KMAX && (dtype == PYTC_BF16 || dtype == PYTC_F32) && tuning_get("conv3d_wgrad_thin", 1) != 0) {
+  } else if (C_k <= SWT_KMAX && (dtype == PYTC_BF16 || dtype == PYTC_F32)) {
     dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO, taps);
     if (dtype == PYTC_BF16)
       hipLaunchKernelGGL(conv3d_wgrad_strided_thin_kernel<bf16_t>, tgrid, block, 0, s, (const bf16_t*)big, (const bf16_t*)small,

@@ -481,18 +481,14 @@ constexpr int MARCH_CG = 32;
 // 340 us as scheduled -- so this removes ~40 % of its issue cycles; the input plane and the taps live in LDS as f16 (half the
 // bytes per read).  Error budget: the bf16 inputs are exact in f16 (8 -> 11 mantissa bits), a 9-term f16 partial sum carries
 // ~sqrt(9) * 2^-12 = 7e-4 relative error, below the 2^-9 rounding of the bf16 result; the z direction stays in fp32.
-// TX / NT: x extent of the footprint and threads per workgroup.  8 / 256 is the original shape; 16 / 512 (two 8 x 8 sub-tiles staged
-// as ONE 10 x 18 haloed plane, same work and registers per thread) shares the halo columns between the sub-tiles inside the
-// workgroup instead of hoping for an L2 hit: x-halo traffic 10/8 -> 18/16, and a row segment of 18 voxels touches 10 cache
-// lines for 8 useful ones where two 10-voxel segments touch 12.
-template <typename T, int VEC, int PF, bool ASYNC, int WPS = 2, bool RES = false, bool H16 = false, int TX = 8, int NT = 256>
-__global__ void __launch_bounds__(NT, WPS)
+template <typename T, int VEC, int PF, bool ASYNC, int WPS = 2, bool RES = false, bool H16 = false>
+__global__ void __launch_bounds__(256, WPS)
 dwconv3d_k3_march_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ w,
                          const float* __restrict__ bias, float* __restrict__ stats, DwMarch g,
                          const T* __restrict__ res = nullptr) {
   // VEC channels per lane (4: ds_read_b128, 108 weight registers; 2: ds_read_b64, 54 weight registers ->
   // more resident workgroups).  PF = planes of global loads kept in flight (register staged).
-  constexpr int TILE_X = TX;
+  constexpr int NT = 256;
   constexpr int CG = MARCH_CG, LPV = CG / VEC, PPP = NT / LPV, PASSES = (TILE_Y * TILE_X) / PPP;
   constexpr int EY = TILE_Y + 2, EX = TILE_X + 2;
   constexpr int EPC = 16 / (int)sizeof(T);          // elements per 16-byte chunk
@@ -801,22 +797,12 @@ dwconv3d_k3_march_kernel(const T* __restrict__ x, T* __restrict__ y, const float
       if (gz + 1 <= ze) { step(gz + 1, slot, accB, accC, accA, stg1, stg2, rq1, rq0); slot ^= 1; }
       if (gz + 2 <= ze) { step(gz + 2, slot, accC, accA, accB, stg2, stg0, rq2, rq1); slot ^= 1; }
     }
-  } else if (PF == 1) {
+  } else {
+    static_assert(PF == 1, "three planes in flight (asm loads) or one (compiler loads)");
     for (int gz = zs - 1; gz <= ze; gz += 3) {
       step(gz, slot, accA, accB, accC, stg0, stg0, rq0, rq2); slot ^= 1;
       if (gz + 1 <= ze) { step(gz + 1, slot, accB, accC, accA, stg0, stg0, rq1, rq0); slot ^= 1; }
       if (gz + 2 <= ze) { step(gz + 2, slot, accC, accA, accB, stg0, stg0, rq2, rq1); slot ^= 1; }
-    }
-  } else {
-    // plane p travels in stg[(p - (zs-1)) & 1]: step k (gz = zs-1+k) loads plane gz+2 into set k&1 and
-    // commits plane gz+1 from set (k+1)&1
-    for (int gz = zs - 1; gz <= ze; gz += 6) {
-      step(gz, slot, accA, accB, accC, stg0, stg1, rq0, rq2); slot ^= 1;
-      if (gz + 1 <= ze) { step(gz + 1, slot, accB, accC, accA, stg1, stg0, rq1, rq0); slot ^= 1; }
-      if (gz + 2 <= ze) { step(gz + 2, slot, accC, accA, accB, stg0, stg1, rq2, rq1); slot ^= 1; }
-      if (gz + 3 <= ze) { step(gz + 3, slot, accA, accB, accC, stg1, stg0, rq0, rq2); slot ^= 1; }
-      if (gz + 4 <= ze) { step(gz + 4, slot, accB, accC, accA, stg0, stg1, rq1, rq0); slot ^= 1; }
-      if (gz + 5 <= ze) { step(gz + 5, slot, accC, accA, accB, stg1, stg0, rq2, rq1); slot ^= 1; }
     }
   }
   if constexpr (ASYNC) asm volatile("s_waitcnt vmcnt(0)" : : : "memory");     // (asm_check.py: the epilogue is reached through a wait)
@@ -859,19 +845,15 @@ static bool march_ok(int D, int H, int W, int C, int K, int stride, int dtype, i
 // footprints handle ragged tiles the same way: bf16 forward launches only (the gather / x-block kernels keep everything else)
 static bool mfma_small_ok(int D, int H, int W, int C, int K, int stride, int dtype, int transposed) {
   if (transposed || K != 3 || stride != 1 || dtype != PYTC_BF16 || (C % MARCH_CG) != 0) return false;
-  if (tuning_get("dwconv_mfma", 1) == 0 || tuning_get("dwconv_mfma_small", 1) == 0) return false;
+  if (tuning_get(K_dwconv_mfma) == 0) return false;
   return D >= 8 && H >= 8 && W >= 8 && (H < 16 || W < 16);
 }
 
-// the forward kernel's footprint: 8 x 16 where the rows divide into whole 16-voxel tiles (level 0: W = 112), 8 x 8 otherwise
-static int march_tile_x(int W, int dtype) {
-  return (dtype == PYTC_BF16 && W % 16 == 0 && tuning_get("dwconv_march_tx16", 0) != 0 && tuning_get("dwconv_mfma", 1) == 0) ? 16 : TILE_X;
-}
-
-static void make_march(DwMarch& t, int N, int D, int H, int W, int C, int tilex = TILE_X) {
+static void make_march(DwMarch& t, int N, int D, int H, int W, int C) {
   t.N = N; t.D = D; t.H = H; t.W = W; t.C = C;
-  t.tilex = tilex;
-  t.ty = (H + TILE_Y - 1) / TILE_Y; t.tx = (W + tilex - 1) / tilex;
+  t.tilex = TILE_X;
+  t.swizzle = 1; t.cg_inner = 1;
+  t.ty = (H + TILE_Y - 1) / TILE_Y; t.tx = (W + TILE_X - 1) / TILE_X;
   // z-chunks: enough workgroups PER SAMPLE to fill the chip (>= 1024: 4 per CU at batch 1), chunks >= 14 planes (halo <= 14 %).
   // The split must not depend on N: the statistics partials (one per workgroup) are summed in slot order, so a sample's
   // mean / rstd -- and with them its bf16 prediction -- would otherwise change with the batch it happens to travel in
@@ -880,14 +862,14 @@ static void make_march(DwMarch& t, int N, int D, int H, int W, int C, int tilex 
   // Measured and removed (round 4): choosing the split that minimises ceil(workgroups / 1024 resident) x (zc + 2) for an 8-window batch
   // (56^3 x 64: 5 chunks instead of 4; 112^3 x 32: 7 instead of 6) changed no launch time (396 / 116 / 41 us either way): the
   // workgroups of these kernels do not advance in rounds, the launch is throughput bound.
-  int nzc = (int)(((long)tuning_get("dwconv_march_wgs", 1024) + fp - 1) / fp);
+  int nzc = (int)((1024 + fp - 1) / fp);
   if (nzc < 1) nzc = 1;
-  // ... unless 14-plane chunks leave a sample with fewer than `dwconv_march_small_wgs` workgroups (the 20^3 x 256 level of MedNeXt-L: 72): such a
+  // ... unless 14-plane chunks leave a sample with fewer than 128 workgroups (the 20^3 x 256 level of MedNeXt-L: 72): such a
   // launch is a chain of D + 2 dependent plane steps on a fraction of the chip, its bytes are irrelevant -- chunks of >= 5 planes then
   // (24.5 -> 16.5 us there; applied to the larger levels the extra halo costs more than it saves: profiles/r05_short_z_chunks.txt).
   // A per-sample rule: the split still does not depend on N.
-  const int min_planes = fp * (D / 14 > 0 ? D / 14 : 1) < (long)tuning_get("dwconv_march_small_wgs", 128) ? 5 : 14;
-  int maxc = D / tuning_get("dwconv_march_min_planes", min_planes);
+  const int min_planes = fp * (D / 14 > 0 ? D / 14 : 1) < 128 ? 5 : 14;
+  int maxc = D / min_planes;
   if (maxc < 1) maxc = 1;
   if (nzc > maxc) nzc = maxc;
   t.zc = (D + nzc - 1) / nzc;
@@ -1118,6 +1100,8 @@ dw_wgrad_march_kernel(const T* __restrict__ gr, const T* __restrict__ x, float* 
 
 static void make_wgrad_march(DwMarch& t, int N, int D, int H, int W, int C) {
   t.N = N; t.D = D; t.H = H; t.W = W; t.C = C;
+  t.tilex = TILE_X;
+  t.swizzle = 1; t.cg_inner = 1;
   t.ty = (H + TILE_Y - 1) / TILE_Y; t.tx = (W + TILE_X - 1) / TILE_X;
   // z-chunks: ~2048 workgroups (each ends with a 3.5 KB partial), chunks of at least 14 planes
   const long fp = (long)t.ty * t.tx * (C / MARCH_CG) * N;
@@ -1133,7 +1117,7 @@ static void make_wgrad_march(DwMarch& t, int N, int D, int H, int W, int C) {
 
 // used by pytc_dw_wgrad (train_kernels.hip): slot count (0 = shape not covered) and launch of the march form
 int dw_wgrad_march_slots(int N, int D, int H, int W, int C, int K, int stride, int dtype) {
-  if (!march_ok(D, H, W, C, K, stride, dtype, 0) || tuning_get("dw_wgrad_march", 1) == 0) return 0;
+  if (!march_ok(D, H, W, C, K, stride, dtype, 0) || tuning_get(K_dw_wgrad_march) == 0) return 0;
   DwMarch t;
   make_wgrad_march(t, N, D, H, W, C);
   return t.slots * N;
@@ -1143,8 +1127,6 @@ void dw_wgrad_march_launch(const void* gr, const void* x, float* dWp, float* dbp
                            int dtype, hipStream_t s) {
   DwMarch t;
   make_wgrad_march(t, N, D, H, W, C);
-  t.swizzle = tuning_get("dwconv_xcd_swizzle", 1);
-  t.cg_inner = tuning_get("dwconv_cg_inner", 1);
   dim3 grid((unsigned)((long)t.slots * (C / MARCH_CG) * N)), block(256);
   if (dtype == PYTC_BF16)
     hipLaunchKernelGGL(dw_wgrad_march_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)gr, (const bf16_t*)x, dWp, dbp, t);
@@ -1222,10 +1204,9 @@ static bool make_geom(DwGeom& g, int N, int D, int H, int W, int C, int K, int s
   }
   g.lpv = C / vec;
   g.vs = 256 / g.lpv;
-  g.cell = (transposed && K == 3 && 27L * C * 4 <= 64 * 1024 && tuning_get("dwconvT_cell", 1) != 0) ? 1 : 0;
-  // K = 5 / 7, stride 1, 16-byte channel vectors, taps fit LDS: 4 consecutive x outputs per lane (dwconv3d_xblock_kernel)
-  g.xblock = (!transposed && stride == 1 && (K == 5 || K == 7 || (K == 3 && tuning_get("dwconv_xblock_k3", 1) != 0)) && vec == 8 &&
-              (long)K * K * K * C * 4 <= 64 * 1024 && tuning_get("dwconv_xblock", 1) != 0 && tuning_get("dwconv_gather", 1) != 0) ? 1 : 0;
+  g.cell = (transposed && K == 3 && 27L * C * 4 <= 64 * 1024) ? 1 : 0;
+  // K = 3 / 5 / 7, stride 1, 16-byte channel vectors, taps fit LDS: 4 consecutive x outputs per lane (dwconv3d_xblock_kernel)
+  g.xblock = (!transposed && stride == 1 && (K == 3 || K == 5 || K == 7) && vec == 8 && (long)K * K * K * C * 4 <= 64 * 1024) ? 1 : 0;
   long vout = g.cell ? (long)D * H * W : (g.xblock ? (long)D * H * ((W + 3) / 4) : (long)g.Do * g.Ho * g.Wo);
   long it = vout / ((long)g.vs * (g.cell ? 256 : 96));   // aim for >= ~96 (cells: 256) workgroups per sample
   g.iters = (int)(it < 1 ? 1 : (it > 64 ? 64 : it));
@@ -1243,7 +1224,7 @@ static int launch_dw(bool transposed, const void* x, void* y, const float* w, co
     hipLaunchKernelGGL((dwconvT3d_k3_cell_kernel<T, VEC>), grid, block, lds > taps ? lds : taps, s, (const T*)x, (T*)y, w, bias, stats, g);
     return PYTC_OK;
   }
-  if (!transposed && (g.K == 3 || g.K == 5 || g.K == 7) && taps <= 64 * 1024 && tuning_get("dwconv_gather", 1) != 0) {
+  if (!transposed && (g.K == 3 || g.K == 5 || g.K == 7) && taps <= 64 * 1024) {
     const size_t dyn = lds > taps ? lds : taps;
     if constexpr (VEC == 8) {
       if (g.stride == 1 && g.xblock) {
@@ -1309,11 +1290,11 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
   // the up blocks' resampling conv at C = 64 / 128: one tile of input cells per workgroup (dwconvT_tile_kernels.hip).  The plan is made
   // FIRST: a shape it rejects falls through to the generic kernels, which take a null output only in their cell form (checked below)
   DwTTile tt;
-  const bool tt_form = transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get("dwconvT_tile", 1) != 0 &&
+  const bool tt_form = transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get(K_dwconvT_tile) != 0 &&
                        dwconvT_tile_plan(tt, N, D, H, W, C);
   // statistics-only passes (null output): the matrix-core stride-1 kernel (the fused block's first pass, pw_dwmix_kernels.hip) and
   // the K = 3 transposed kernels (tile form / cell form: the fused up-block path)
-  const bool mfma_form = !transposed && !res && !wide_range && dtype == PYTC_BF16 && tuning_get("dwconv_mfma", 1) != 0 &&
+  const bool mfma_form = !transposed && !res && !wide_range && dtype == PYTC_BF16 && tuning_get(K_dwconv_mfma) != 0 &&
                          (march_ok(D, H, W, C, K, stride, dtype, transposed) || mfma_small_ok(D, H, W, C, K, stride, dtype, transposed));
   if (!y) {
     PYTC_REQUIRE(stats, "dwconv3d: neither output nor statistics requested");
@@ -1330,7 +1311,7 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
     PYTC_LAUNCH_CHECK("dwconvT3d_k3_tile");
     return PYTC_OK;
   }
-  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && y && tuning_get("dwconv_s2_march", 1) != 0) {
+  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && y && tuning_get(K_dwconv_s2_march) != 0) {
     DwS2 t2;          // the down blocks' resampling conv at C = 32 / 64: z-march over an LDS ring (dwconv_s2_kernels.hip)
     if (dwconv_s2_plan(t2, N, D, H, W, C)) {
       dwconv_s2_launch(x, y, w, bias, stats, t2, (hipStream_t)stream);
@@ -1340,42 +1321,30 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
   }
   if (!res && !wide_range && mfma_small_ok(D, H, W, C, K, stride, dtype, transposed)) {
     DwMarch t;
-    make_march(t, N, D, H, W, C, TILE_X);
-    t.swizzle = tuning_get("dwconv_xcd_swizzle", 1);
-    t.cg_inner = tuning_get("dwconv_cg_inner", 1);
+    make_march(t, N, D, H, W, C);
     // hi + lo weights here: these launches are latency bound (22 us either way), and with bf16 weights at the 14^3 level the
     // training gate's worst tensor (bottleneck.1.norm.weight) moved from 0.050 to 0.066 relative L2 against a 0.05 class
-    dwconv_mfma_launch(x, y, w, bias, stats, t, tuning_get("dwconv_mfma_variant", 0) | 1, (hipStream_t)stream);
+    dwconv_mfma_launch(x, y, w, bias, stats, t, tuning_get(K_dwconv_mfma_variant) | 1, (hipStream_t)stream);
     PYTC_LAUNCH_CHECK("dwconv3d_k3_mfma");
     return PYTC_OK;
   }
   if (march_ok(D, H, W, C, K, stride, dtype, transposed)) {
     DwMarch t;
-    // the 8 x 16 / 512-thread footprint serves the plain packed-f16 forward (the launches that carry statistics, so the slot
-    // count of pytc_dwconv3d_stat_slots follows the same rule); gradient entries keep the 8 x 8 kernels
-    const bool wide_tile = !res && !wide_range && tuning_get("dwconv_march_h16", 1) != 0 && march_tile_x(W, dtype) == 16;
-    make_march(t, N, D, H, W, C, wide_tile ? 16 : TILE_X);
-    dim3 grid((unsigned)((long)t.slots * (C / MARCH_CG) * N)), block(wide_tile ? 512 : 256);
-    t.swizzle = tuning_get("dwconv_xcd_swizzle", 1);
-  t.cg_inner = tuning_get("dwconv_cg_inner", 1);
+    make_march(t, N, D, H, W, C);
+    dim3 grid((unsigned)((long)t.slots * (C / MARCH_CG) * N)), block(256);
     // bf16 forward launches (activations: statistics, no residual): the matrix-core form (dwconv_mfma_kernels.hip) -- one channel per
     // block of v_mfma_f32_4x4x4_16b_bf16, fp32 accumulation.  The gradient entries (res / wide range) keep the fp32-tap VALU kernels.
-    if (dtype == PYTC_BF16 && !res && !wide_range && tuning_get("dwconv_mfma", 1) != 0) {
-      dwconv_mfma_launch(x, y, w, bias, stats, t, tuning_get("dwconv_mfma_variant", 0), (hipStream_t)stream);
+    if (dtype == PYTC_BF16 && !res && !wide_range && tuning_get(K_dwconv_mfma) != 0) {
+      dwconv_mfma_launch(x, y, w, bias, stats, t, tuning_get(K_dwconv_mfma_variant), (hipStream_t)stream);
       PYTC_LAUNCH_CHECK("dwconv3d_k3_mfma");
       return PYTC_OK;
     }
-    // variants (all: taps in LDS, hand-scheduled tap loop, asm plane loads with counted waits):
-    //   0 (default) PF=3 compiled for 4 waves/SIMD; 1: PF=3, 3 waves; 2: PF=3, 2 waves; 3: PF=2, 3 waves
-    const int variant = tuning_get("dwconv_march_variant", 0);
-#define PYTC_MARCH(PP, WW) \
-  hipLaunchKernelGGL((dwconv3d_k3_march_kernel<bf16_t, 2, PP, true, WW>), grid, block, 0, (hipStream_t)stream, \
-                     (const bf16_t*)x, (bf16_t*)y, w, bias, stats, t)
+    // all forms: taps in LDS, hand-scheduled tap loop; bf16: asm plane loads with counted waits, three planes in flight
     // packed-f16 in-plane partial sums (see the kernel header); 0: fp32 taps.  f16 resolves 6e-8 at best: it is for ACTIVATIONS.
     // Gradient operands (a mean-reduced loss over 1.4 M voxels gives |dL/dx| ~ 1e-7) sit in its subnormal range -- measured:
     // every parameter gradient behind the last block off by 35-85 % at 112^3 (tests/test_gpu_baseline_sizes.py training gate,
     // profiles/r03_training_gradient_gate.txt) -- so the residual / wide-range entries always take the fp32-tap kernel
-    const int h16 = (res || wide_range) ? 0 : tuning_get("dwconv_march_h16", 1);
+    const int h16 = (res || wide_range) ? 0 : tuning_get(K_dwconv_march_h16);
     if (res) {
       // 8 more live registers than the plain kernel (two residual sets in flight): compiled for 3 waves / SIMD.  At the
       // 4-waves budget (128 VGPRs) hipcc spills 31 registers, and a spill of a register an asm-issued load is still
@@ -1386,24 +1355,16 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
       else
         hipLaunchKernelGGL((dwconv3d_k3_march_kernel<bf16_t, 2, 3, true, 3, true>), grid, block, 0, (hipStream_t)stream,
                            (const bf16_t*)x, (bf16_t*)y, w, bias, stats, t, (const bf16_t*)res);
-    } else if (dtype == PYTC_BF16 && h16 && wide_tile) {
-      hipLaunchKernelGGL((dwconv3d_k3_march_kernel<bf16_t, 2, 3, true, 2, false, true, 16, 512>), grid, block, 0, (hipStream_t)stream,
-                         (const bf16_t*)x, (bf16_t*)y, w, bias, stats, t);
     } else if (dtype == PYTC_BF16 && h16) {
       hipLaunchKernelGGL((dwconv3d_k3_march_kernel<bf16_t, 2, 3, true, 4, false, true>), grid, block, 0, (hipStream_t)stream,
                          (const bf16_t*)x, (bf16_t*)y, w, bias, stats, t);
     } else if (dtype == PYTC_BF16) {
-      switch (variant) {
-        case 1: PYTC_MARCH(3, 3); break;
-        case 2: PYTC_MARCH(3, 2); break;
-        case 3: PYTC_MARCH(2, 3); break;
-        default: PYTC_MARCH(3, 4); break;
-      }
+      hipLaunchKernelGGL((dwconv3d_k3_march_kernel<bf16_t, 2, 3, true, 4>), grid, block, 0, (hipStream_t)stream,
+                         (const bf16_t*)x, (bf16_t*)y, w, bias, stats, t);
     } else {
       hipLaunchKernelGGL((dwconv3d_k3_march_kernel<float, 2, 1, false, 2>), grid, block, 0, (hipStream_t)stream,
                          (const float*)x, (float*)y, w, bias, stats, t);
     }
-#undef PYTC_MARCH
     PYTC_LAUNCH_CHECK("dwconv3d_k3_march");
     return PYTC_OK;
   }
@@ -1429,19 +1390,19 @@ extern "C" int pytc_dwconv3d_stat_slots(int N, int D, int H, int W, int C, int K
                                         int transposed) {
   if (march_ok(D, H, W, C, K, stride, dtype, transposed)) {
     DwMarch t;
-    make_march(t, N, D, H, W, C, tuning_get("dwconv_march_h16", 1) != 0 ? march_tile_x(W, dtype) : TILE_X);
+    make_march(t, N, D, H, W, C);
     return t.slots;
   }
   if (mfma_small_ok(D, H, W, C, K, stride, dtype, transposed)) {
     DwMarch t;
-    make_march(t, N, D, H, W, C, TILE_X);
+    make_march(t, N, D, H, W, C);
     return t.slots;
   }
-  if (transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get("dwconvT_tile", 1) != 0) {
+  if (transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get(K_dwconvT_tile) != 0) {
     DwTTile tt;
     if (dwconvT_tile_plan(tt, N, D, H, W, C)) return tt.slots;
   }
-  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && tuning_get("dwconv_s2_march", 1) != 0) {
+  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && tuning_get(K_dwconv_s2_march) != 0) {
     DwS2 t2;
     if (dwconv_s2_plan(t2, N, D, H, W, C)) return t2.slots;
   }
@@ -1453,16 +1414,16 @@ extern "C" int pytc_dwconv3d_stat_slots(int N, int D, int H, int W, int C, int K
 
 extern "C" int pytc_dwconv3d_kernel_variant(int N, int D, int H, int W, int C, int K, int stride, int dtype, int transposed) {
   // mirrors dw_entry / launch_dw: which kernel family a call with these arguments dispatches to
-  if (march_ok(D, H, W, C, K, stride, dtype, transposed)) return (dtype == PYTC_BF16 && tuning_get("dwconv_mfma", 1) != 0) ? 6 : 3;
+  if (march_ok(D, H, W, C, K, stride, dtype, transposed)) return (dtype == PYTC_BF16 && tuning_get(K_dwconv_mfma) != 0) ? 6 : 3;
   if (mfma_small_ok(D, H, W, C, K, stride, dtype, transposed)) return 6;
   DwGeom g;
   int vec;
   if (!make_geom(g, N, D, H, W, C, K, stride, dtype, transposed, vec)) return -1;
-  if (transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get("dwconvT_tile", 1) != 0) return 7;
-  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && (C == 32 || C == 64) && tuning_get("dwconv_s2_march", 1) != 0) return 8;
+  if (transposed && K == 3 && dtype == PYTC_BF16 && (C == 64 || C == 128) && tuning_get(K_dwconvT_tile) != 0) return 7;
+  if (!transposed && K == 3 && stride == 2 && dtype == PYTC_BF16 && (C == 32 || C == 64) && tuning_get(K_dwconv_s2_march) != 0) return 8;
   if (transposed) return g.cell ? 4 : 5;
   const size_t taps = (size_t)K * K * K * C * sizeof(float);
-  if ((K == 3 || K == 5 || K == 7) && taps <= 64 * 1024 && tuning_get("dwconv_gather", 1) != 0)
+  if ((K == 3 || K == 5 || K == 7) && taps <= 64 * 1024)
     return (vec == 8 && stride == 1 && g.xblock) ? 2 : 1;
   return 0;
 }
@@ -1488,7 +1449,7 @@ extern "C" int pytc_dwconv3d_fwd_res(const void* x, const void* res, void* y, co
 }
 
 extern "C" int pytc_dwmix_supported(int D, int H, int W, int C, int C_hid, int C_out, int dtype) {
-  return (dtype == PYTC_BF16 && C == 32 && C_out == 32 && (C_hid == 64 || C_hid == 96 || C_hid == 128) && tuning_get("dwconv_mfma", 1) != 0 &&
+  return (dtype == PYTC_BF16 && C == 32 && C_out == 32 && (C_hid == 64 || C_hid == 96 || C_hid == 128) && tuning_get(K_dwconv_mfma) != 0 &&
           (march_ok(D, H, W, C, 3, 1, dtype, 0) || mfma_small_ok(D, H, W, C, 3, 1, dtype, 0))) ? 1 : 0;
 }
 
@@ -1502,20 +1463,15 @@ extern "C" int pytc_dwmix_fwd(const void* x, const float* taps, const float* dw_
   PYTC_REQUIRE(y || (head_w && head_y), "dwmix: neither the block output nor the head output requested");
   PYTC_REQUIRE(!head_w || (head_y && n_head >= 1 && n_head <= 16), "dwmix: the fused head writes 1..16 channels to head_y");
   DwMarch t;
-  make_march(t, N, D, H, W, C, TILE_X);
-  t.swizzle = tuning_get("dwconv_xcd_swizzle", 1);
-  t.cg_inner = tuning_get("dwconv_cg_inner", 1);
+  make_march(t, N, D, H, W, C);
   DwMix mx{};
   mx.w2n = (const bf16x8_t*)w2n; mx.b2n = b2n; mx.w3 = (const h8_t*)w3_f16; mx.b3 = b3;
   mx.w2_stride = (long)C_hid * C / 8;
   mx.residual = residual ? 1 : 0;
   mx.head_w = (const bf16x8_t*)head_w; mx.head_b = head_b; mx.head_y = head_y; mx.n_head = n_head; mx.store_y = y ? 1 : 0;
-  // measurement only (knob dwconv_mfma_probe = 4): the address of a [N][slots][4][9] fp32 buffer in the knobs dwmix_prof_lo / _hi
-  if (tuning_get("dwconv_mfma_probe", 0) == 4)
-    mx.prof = (float*)(((unsigned long long)(unsigned)tuning_get("dwmix_prof_hi", 0) << 32) | (unsigned)tuning_get("dwmix_prof_lo", 0));
   // the statistics this block was normalised with are those of pytc_dwconv3d_fwd(y = NULL) under the same knobs: same variant here
   // (small planes -- the 8 <= H, W < 16 launches -- always carry hi + lo weights there)
-  int variant = tuning_get("dwconv_mfma_variant", 0);
+  int variant = tuning_get(K_dwconv_mfma_variant);
   if (!march_ok(D, H, W, C, 3, 1, dtype, 0)) variant |= 1;
   PYTC_REQUIRE(dwmix_launch(x, y, taps, dw_bias, t, mx, C_hid, variant, (hipStream_t)stream) == 0, "dwmix: unsupported hidden width");
   PYTC_LAUNCH_CHECK("dwmix");

@@ -7,10 +7,10 @@ namespace pytc {
 struct DwMarch {
   int N, D, H, W, C;
   int ty, tx, zc, nzc;   // footprints per axis, z-chunk length, z-chunks
-  int tilex;             // x extent of a footprint (8, or 16 for the 512-thread forward variant)
+  int tilex;             // x extent of a footprint (8)
   int slots;             // workgroups per (sample, channel group)
-  int swizzle;           // XCD-aware block remap on/off
-  int cg_inner;          // block order: channel group fastest (else slot fastest)
+  int swizzle;           // XCD-aware block remap on/off (always on)
+  int cg_inner;          // block order: channel group fastest (else slot fastest; always 1)
 };
 
 // dwconv_mfma_kernels.hip: bf16, K = 3, stride 1, C % 32 == 0, 8 x 8 footprints (g.tilex == 8); grid = slots * (C / 32) * N blocks.
@@ -31,7 +31,6 @@ struct DwMix {
   const float* head_b;
   float* head_y;           // [N][D*H*W][n_head] fp32
   int n_head, store_y;
-  float* prof;             // PROBE 4 only (knob dwconv_mfma_probe = 4): [N][slots][4 waves][8] section cycle sums
 };
 int dwmix_launch(const void* x, void* y, const float* w, const float* bias, const DwMarch& g, const DwMix& mx, int c_hid, int variant,
                  hipStream_t s);
@@ -42,7 +41,7 @@ bool dwconvT_tile_plan(DwTTile& g, int N, int D, int H, int W, int C);
 void dwconvT_tile_launch(const void* x, void* y, const float* w, const float* bias, float* stats, const DwTTile& g, hipStream_t s);
 
 // dwconv_s2_kernels.hip: K = 3 / stride 2 conv of the down blocks, bf16, C = 32 / 64, z-march over an LDS ring of input planes
-struct DwS2 { int N, D, H, W, C, Do, Ho, Wo, ty, tx, zc, nzc, slots, tyo; };
+struct DwS2 { int N, D, H, W, C, Do, Ho, Wo, ty, tx, zc, nzc, slots; };
 bool dwconv_s2_plan(DwS2& g, int N, int D, int H, int W, int C);
 void dwconv_s2_launch(const void* x, void* y, const float* w, const float* bias, float* stats, const DwS2& g, hipStream_t s);
 

@@ -67,10 +67,6 @@ template <int N>
 __device__ __forceinline__ void mf_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 
 // PF: planes in flight (register staged).  LO: second instruction per operand with the low halves of the weights.
-// PROBE (timing probes, wrong results): 1 = no matrix instructions, 3 = no matrix instructions and no output path;
-// 4 = right results, and instead of the statistics every wave leaves the shader cycles (s_memtime) it spent in each section of its
-// plane steps -- stats[(n, slot, 0, cg*32 + wave*8 + k)], k = 0 flush + load issue, 1 matrix instructions, 2 wait for the staged
-// plane, 3 LDS commit, 4 output rounding + tile writes, 5 barrier, 6 steps, 7 whole kernel (profiles/r05_additivity.txt).
 // STORE = false: the statistics-only pass of the fused block (pw_dwmix_kernels.hip): same products, same rounding, same partial sums
 // in the same order as the storing kernel (bit-identical statistics) -- the output tile, its LDS traffic and the HBM stores are gone.
 // MIXHC > 0: the FUSED BLOCK (round 5; C = 32, C_out = 32, hidden width 32 * MIXHC): the depthwise output of a plane goes no
@@ -92,7 +88,7 @@ __device__ __forceinline__ void mf_wait_vm_upto(int n) {     // s_waitcnt vmcnt(
   }
 }
 
-template <int PF, bool LO, int PROBE = 0, bool STORE = true, int MIXHC = 0>
+template <int PF, bool LO, bool STORE = true, int MIXHC = 0>
 __global__ void __launch_bounds__(256, MIXHC ? 3 : 4)
 dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, const float* __restrict__ w,
                         const float* __restrict__ bias, float* __restrict__ stats, DwMarch g, DwMix mx) {
@@ -312,17 +308,6 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
 #pragma unroll
     for (int r = 0; r < 2; ++r) acc[u][r] = f32x4_t{bv, bv, bv, 0.f};
   float s1 = 0.f, s2 = 0.f;
-  // PROBE 4: per-section cycle sums of this wave (wave-uniform values; s_memtime waits on lgkmcnt, i.e. also drains the wave's own
-  // LDS operations at each stamp: the sections are slightly serialised against the untimed kernel, +5 % launch time measured)
-  unsigned long long tk[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0, tstart = 0;
-  auto stamp = [&](int k) {
-    if constexpr (PROBE == 4) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      tk[k] += now - tlast;
-      tlast = now;
-    }
-  };
-  if constexpr (PROBE == 4) { tstart = __builtin_amdgcn_s_memtime(); tlast = tstart; }
 
   // one z step: input plane gz is image[slot]; `ld` receives plane gz+PF, `cm` holds plane gz+1 and is committed after the compute
   // (fused block: `rn` receives the residual rows of plane gz, `ro` holds those of plane gz - 2)
@@ -332,17 +317,15 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
     if constexpr (MIX) {
       // requested after R(gz - 2): P(gz + 1), then R(gz - 1), P(gz + 2) (request order within a step: residual, then plane)
       if (gz - 2 >= zs) mix(gz - 2, ro, (exists_p(gz + 1) ? MF_CPT : 0) + (exists_r(gz - 1) ? 1 : 0) + (exists_p(gz + 2) ? MF_CPT : 0));
-      stamp(8);
       if (exists_r(gz)) issue_res(gz, rn);
     } else {
-      if (STORE && gz - 2 >= zs && PROBE != 3) flush(gz - 2);
+      if (STORE && gz - 2 >= zs) flush(gz - 2);
     }
     if (gz + PF <= ze) issue(gz + PF, ld);
-    stamp(0);
     // ---- the stencil of this plane: 3 row offsets x (2 output columns x hi/lo) instructions per unit
     const unsigned short* img = image[slot];
 #pragma unroll
-    for (int dy = 0; dy < ((PROBE == 1 || PROBE == 3) ? 0 : 3); ++dy) {
+    for (int dy = 0; dy < 3; ++dy) {
       s4_t bq[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) bq[u] = __builtin_bit_cast(s4_t, *reinterpret_cast<const u32x2a4_t*>(img + boff[u] + dy * MF_EXP));
@@ -357,15 +340,12 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
           for (int r = 0; r < 2; ++r) acc[u][r] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a_lo[dy][r], bq[u], acc[u][r], 0, 0, 0);
       }
     }
-    stamp(1);
     // ---- plane gz+1 into the other image slot
     if (gz + 1 <= ze) {
       // loads requested after plane gz+1: planes gz+2 .. gz+PF as far as the chunk goes, and (fused block) the residual rows of the
       // steps in between: R(gz - 1) and R(gz) at PF = 3
       landed(cm, MF_CPT * min(PF - 1, ze - gz - 1) + (exists_r(gz - 1) ? 1 : 0) + (exists_r(gz) ? 1 : 0));
-      stamp(2);
       commit(slot ^ 1, cm, gz + 1);
-      stamp(3);
     } else {
       // last step of the chunk: nothing is in flight any more.  The statement is here for csrc/asm_check.py: EVERY path through a step
       // executes a hand-written vmcnt wait after the step's load requests, so "no compiler instruction touches a staged register
@@ -374,7 +354,7 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
     }
     // ---- output plane gz-1 is complete: accumulator VGPR 0, lane = (channel, column) -> the workgroup's NDHWC tile of parity
     //      (gz-1) & 1; it leaves at the start of the next step, after this step's barrier
-    if (gz - 1 >= zs && PROBE != 3) {
+    if (gz - 1 >= zs) {
       unsigned short* ot = otile[STORE ? (gz - 1) & 1 : 0];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -397,10 +377,7 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int r = 0; r < 2; ++r) acc[u][r] = f32x4_t{acc[u][r][1], acc[u][r][2], bv, 0.f};
-    stamp(4);
     __syncthreads();
-    stamp(5);
-    if constexpr (PROBE == 4) tk[6] += 1;
   };
 
   // prologue: plane zs-1 -> image 0; planes zs (.. zs+1) already in flight.  Plane p travels in set (p - (zs-1)) % PF: step k
@@ -426,25 +403,9 @@ dwconv3d_k3_mfma_kernel(const unsigned short* __restrict__ x, unsigned short* __
     else if (rs == 1) mix(ze - 1, rres[MIX ? 1 : 0], 0);
     else mix(ze - 1, rres[MIX ? 2 : 0], 0);
   } else {
-    if (STORE && PROBE != 3) flush(ze - 1);
+    if (STORE) flush(ze - 1);
   }
 
-  if constexpr (PROBE == 4) {
-    if constexpr (MIX) {
-      if (mx.prof && lane == 0) {      // [N][slots][4 waves][9]: sections 0..7 as below, 8 = channel mixer (incl. its wait for the residual rows)
-        tk[7] = __builtin_amdgcn_s_memtime() - tstart;
-        float* o = mx.prof + (((long)n * g.slots + slot_id) * 4 + wave) * 9;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) o[k] = (float)tk[k];
-      }
-    } else if (stats && lane == 0) {
-      tk[7] = __builtin_amdgcn_s_memtime() - tstart;
-      float* o = stats + (((long)n * g.slots + slot_id) * 2) * C + cg * MF_CG + wave * 8;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (float)tk[k];
-    }
-    return;
-  }
   if (!MIX && stats) {
     s1 += __shfl_xor(s1, 1, 64); s2 += __shfl_xor(s2, 1, 64);
     s1 += __shfl_xor(s1, 2, 64); s2 += __shfl_xor(s2, 2, 64);
@@ -464,21 +425,16 @@ void dwconv_mfma_launch(const void* x, void* y, const float* w, const float* bia
   const unsigned short* xp = (const unsigned short*)x;
   unsigned short* yp = (unsigned short*)y;
   const DwMix none{};
-#define PYTC_MF(PFV, LOV, NM) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<PFV, LOV, NM>), grid, block, 0, s, xp, yp, w, bias, stats, g, none)
-#define PYTC_MF_STATS(PFV, LOV) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<PFV, LOV, 0, false>), grid, block, 0, s, xp, yp, w, bias, stats, g, none)
+#define PYTC_MF(PFV, LOV) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<PFV, LOV>), grid, block, 0, s, xp, yp, w, bias, stats, g, none)
+#define PYTC_MF_STATS(PFV, LOV) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<PFV, LOV, false>), grid, block, 0, s, xp, yp, w, bias, stats, g, none)
   // variant: bit 0 = hi + lo weight instructions (16-bit weight mantissa; default: hi only = bf16 weights, what torch.autocast gives the
-  // reference's Conv3d), bit 1 = two planes in flight instead of three.  Knob dwconv_mfma_probe (1 / 3; measurements only, WRONG results):
-  // the kernel without its matrix instructions / without them and without the output path.
-  const int probe = tuning_get("dwconv_mfma_probe", 0);
+  // reference's Conv3d), bit 1 = two planes in flight instead of three
   if (!y) {                                           // statistics only (dw_entry has checked that statistics are requested)
     if (variant & 1) { if (variant & 2) PYTC_MF_STATS(2, true); else PYTC_MF_STATS(3, true); }
     else { if (variant & 2) PYTC_MF_STATS(2, false); else PYTC_MF_STATS(3, false); }
   }
-  else if (probe == 1) PYTC_MF(3, false, 1);
-  else if (probe == 3) PYTC_MF(3, false, 3);
-  else if (probe == 4) PYTC_MF(3, false, 4);
-  else if (variant & 1) { if (variant & 2) PYTC_MF(2, true, 0); else PYTC_MF(3, true, 0); }
-  else { if (variant & 2) PYTC_MF(2, false, 0); else PYTC_MF(3, false, 0); }
+  else if (variant & 1) { if (variant & 2) PYTC_MF(2, true); else PYTC_MF(3, true); }
+  else { if (variant & 2) PYTC_MF(2, false); else PYTC_MF(3, false); }
 #undef PYTC_MF
 #undef PYTC_MF_STATS
 }
@@ -490,17 +446,12 @@ int dwmix_launch(const void* x, void* y, const float* w, const float* bias, cons
   dim3 grid((unsigned)((long)g.slots * g.N)), block(256);
   const unsigned short* xp = (const unsigned short*)x;
   unsigned short* yp = (unsigned short*)y;
-#define PYTC_DM(LOV, HCV, PRB) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<3, LOV, PRB, true, HCV>), grid, block, 0, s, xp, yp, w, bias, (float*)nullptr, g, mx)
+#define PYTC_DM(LOV, HCV) hipLaunchKernelGGL((dwconv3d_k3_mfma_kernel<3, LOV, true, HCV>), grid, block, 0, s, xp, yp, w, bias, (float*)nullptr, g, mx)
   const bool lo = variant & 1;
-  if (mx.prof) {                        // measurement only: section cycle counters (tools/r05_additivity.py phases_mix)
-    if (c_hid != 64 || lo) return -1;
-    PYTC_DM(false, 2, 4);
-    return 0;
-  }
   switch (c_hid) {
-    case 64: if (lo) PYTC_DM(true, 2, 0); else PYTC_DM(false, 2, 0); break;
-    case 96: if (lo) PYTC_DM(true, 3, 0); else PYTC_DM(false, 3, 0); break;
-    case 128: if (lo) PYTC_DM(true, 4, 0); else PYTC_DM(false, 4, 0); break;
+    case 64: if (lo) PYTC_DM(true, 2); else PYTC_DM(false, 2); break;
+    case 96: if (lo) PYTC_DM(true, 3); else PYTC_DM(false, 3); break;
+    case 128: if (lo) PYTC_DM(true, 4); else PYTC_DM(false, 4); break;
     default: return -1;
   }
 #undef PYTC_DM

@@ -14,11 +14,13 @@
 
 namespace pytc {
 
-template <int C, int TYO>
+constexpr int S2_TYO = 4;      // output rows of a footprint: 4 x 8 outputs, 31 KB of LDS at C = 32, four workgroups per CU (8 x 8: 60 KB, two; 5 % slower)
+
+template <int C>
 __global__ void __launch_bounds__(256, 2)
 dwconv3d_k3_s2_march_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, const float* __restrict__ w,
                             const float* __restrict__ bias, float* __restrict__ stats, DwS2 g) {
-  constexpr int TXO = 8, IY = 2 * TYO + 1, IX = 2 * TXO + 1;
+  constexpr int TYO = S2_TYO, TXO = 8, IY = 2 * TYO + 1, IX = 2 * TXO + 1;
   constexpr int LPV = C / 2, VS = 256 / LPV, OUTV = TYO * TXO, ITEMS = OUTV / VS;
   constexpr int PCH = IY * IX * (C / 8);               // 16-byte chunks per input plane
   constexpr int LPT = (PCH + 255) / 256;               // chunks per thread and plane
@@ -159,8 +161,7 @@ dwconv3d_k3_s2_march_kernel(const unsigned short* __restrict__ x, unsigned short
 
 bool dwconv_s2_plan(DwS2& g, int N, int D, int H, int W, int C) {
   if (C != 32 && C != 64) return false;
-  const int tyo = (C == 32 && tuning_get("dwconv_s2_tyo4", 1) == 0) ? 8 : 4;   // 4 x 8 outputs: 31 KB of LDS, four workgroups per CU (8 x 8: 60 KB, two; 5 % slower)
-  g.tyo = tyo;
+  constexpr int tyo = S2_TYO;
   g.N = N; g.D = D; g.H = H; g.W = W; g.C = C;
   g.Do = (D - 1) / 2 + 1; g.Ho = (H - 1) / 2 + 1; g.Wo = (W - 1) / 2 + 1;
   g.ty = (g.Ho + tyo - 1) / tyo; g.tx = (g.Wo + 7) / 8;
@@ -179,15 +180,14 @@ void dwconv_s2_launch(const void* x, void* y, const float* w, const float* bias,
   dim3 grid((unsigned)g.slots, (unsigned)g.N), block(256);
   const unsigned short* xp = (const unsigned short*)x;
   unsigned short* yp = (unsigned short*)y;
-#define PYTC_S2(CC, TYY)                                                                                                      \
+#define PYTC_S2(CC)                                                                                                           \
   do {                                                                                                                        \
-    const size_t lds = (size_t)(3 * (2 * TYY + 1) * 17 * CC + TYY * 8 * CC) * 2;                                               \
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&dwconv3d_k3_s2_march_kernel<CC, TYY>), 72 * 1024, "dwconv3d_k3_s2_march")) return; \
-    hipLaunchKernelGGL((dwconv3d_k3_s2_march_kernel<CC, TYY>), grid, block, lds, s, xp, yp, w, bias, stats, g);               \
+    const size_t lds = (size_t)(3 * (2 * S2_TYO + 1) * 17 * CC + S2_TYO * 8 * CC) * 2;                                         \
+    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&dwconv3d_k3_s2_march_kernel<CC>), 72 * 1024, "dwconv3d_k3_s2_march")) return; \
+    hipLaunchKernelGGL((dwconv3d_k3_s2_march_kernel<CC>), grid, block, lds, s, xp, yp, w, bias, stats, g);                    \
   } while (0)
-  if (g.C == 32 && g.tyo == 8) PYTC_S2(32, 8);
-  else if (g.C == 32) PYTC_S2(32, 4);
-  else PYTC_S2(64, 4);
+  if (g.C == 32) PYTC_S2(32);
+  else PYTC_S2(64);
 #undef PYTC_S2
 }
 

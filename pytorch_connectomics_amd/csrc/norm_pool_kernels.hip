@@ -299,7 +299,7 @@ extern "C" int pytc_affine_act(const void* x, void* y, const float* ab, int N, i
   PYTC_REQUIRE(x && y && N >= 1 && rows >= 1 && C >= 1, "affine_act: bad arguments");
   const long total = (long)N * rows * C;
   const int vec = dtype == PYTC_BF16 ? 8 : 4;
-  if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get("elementwise_vec", 1)) {
+  if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
     const long chunks = total / vec;
     const int vb = (int)((chunks + 255) / 256 < 16384 ? (chunks + 255) / 256 : 16384);
     if (dtype == PYTC_BF16)

@@ -163,8 +163,7 @@ static void launch_fast(const PwFastParams& p, int N, hipStream_t s) {
   // deep levels (level 3: 172 row blocks, bottleneck: 22 for 256 CUs): the output-channel pairs are shared out over blockIdx.z
   // until ~2 workgroups per CU exist; every share re-reads the operand rows (L2 hits: the whole tensor is a few MB there)
   int zsplit = 1;
-  if (tuning_get("pw_fast_zsplit", 1))
-    while (row_blocks * zsplit < 512 && (p.C_out / 32) % (zsplit * 2) == 0) zsplit *= 2;
+  while (row_blocks * zsplit < 512 && (p.C_out / 32) % (zsplit * 2) == 0) zsplit *= 2;
   dim3 grid((unsigned)((p.rps + rows_per_block - 1) / rows_per_block), (unsigned)N, (unsigned)zsplit), block(256);
   hipLaunchKernelGGL((pw_fast_kernel<KS, NT>), grid, block, 0, s, p);
 }
@@ -186,11 +185,10 @@ void pw_fast_launch(const pytc_pw_args* a, const EpiParams& e, hipStream_t s) {
     p.Hi = a->Hi; p.Wi = a->Wi; p.Ho = (a->Hi - 1) / 2 + 1; p.Wo = (a->Wi - 1) / 2 + 1;
     p.rps_in = (long)a->Di * a->Hi * a->Wi;
   }
-  const int nt_knob = tuning_get("pw_fast_nt", 0);
   switch (a->C_in / 32) {
-    case 1: if (nt_knob == 2) launch_fast<1, 2>(p, a->N, s); else launch_fast<1, 4>(p, a->N, s); break;
-    case 2: if (nt_knob == 2) launch_fast<2, 2>(p, a->N, s); else launch_fast<2, 4>(p, a->N, s); break;
-    case 4: if (nt_knob == 4) launch_fast<4, 4>(p, a->N, s); else launch_fast<4, 2>(p, a->N, s); break;
+    case 1: launch_fast<1, 4>(p, a->N, s); break;
+    case 2: launch_fast<2, 4>(p, a->N, s); break;
+    case 4: launch_fast<4, 2>(p, a->N, s); break;
     case 8: launch_fast<8, 2>(p, a->N, s); break;
     case 16: launch_fast<16, 1>(p, a->N, s); break;
     default: launch_fast<32, 1>(p, a->N, s); break;

@@ -272,12 +272,11 @@ extern "C" int pytc_pw_gemm_fwd(const void* x, const void* w, const float* bias,
   hipStream_t s = (hipStream_t)stream;
   // 128-row workgroups once they alone fill the chip twice over, 64-row ones below (the bottleneck level: 2 744 rows)
   const long tiles128 = (p.rows_total + 127) / 128 * (C_out / GEMM_BN);
-  const bool big = tiles128 >= 512 && tuning_get("pw_gemm_rows", 0) != 64;
+  const bool big = tiles128 >= 512 && tuning_get(K_pw_gemm_rows) != 64;
   // 32-wide k steps for the short-K (expanding) GEMMs, 64-wide for the long-K (projecting) ones: MI355X, profiles/r05_gemm_k_step.txt --
   // 256 -> 2048 on 16 000 rows 51 -> 46 us, 512 -> 1024 on 21 952 rows 61 -> 57; 2048 -> 256 34 -> 40 (a barrier per 32 k over 64 steps)
-  const int ks_knob = tuning_get("pw_gemm_ks", 0);
-  const bool ks32 = ks_knob ? ks_knob == 32 : C_in <= 512;
-  if (big || tuning_get("pw_gemm_rows", 0) == 128) {
+  const bool ks32 = C_in <= 512;
+  if (big || tuning_get(K_pw_gemm_rows) == 128) {
     dim3 grid((unsigned)((p.rows_total + 127) / 128 * (C_out / GEMM_BN)));
     if (ks32) {
       if (in_f16) hipLaunchKernelGGL((pw_gemm_lds_kernel<true, 128, 32>), grid, dim3(256), 0, s, p);

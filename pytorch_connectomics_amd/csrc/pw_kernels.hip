@@ -294,7 +294,7 @@ extern "C" int pytc_pw_conv_fwd(const pytc_pw_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int ti = a->in_dtype, tw = a->w_dtype, to = a->out_dtype;
   const bool plain = !a->ab && a->pre_act == PYTC_ACT_NONE && a->res_mode == PYTC_RES_NONE && a->gather == 0 && !a->w_paired &&
-                     tuning_get("pw_thin", 1) != 0;
+                     tuning_get(K_pw_thin) != 0;
   const long rows_total = (long)a->N * a->rows_per_sample;
   if (plain && a->C_in == 1 && a->C_out % 8 == 0 && 256 % (a->C_out / 8) == 0 && tw == PYTC_BF16 && (ti == PYTC_F32 || ti == PYTC_BF16) && to == PYTC_BF16) {
     const long work = rows_total * (a->C_out / 8);

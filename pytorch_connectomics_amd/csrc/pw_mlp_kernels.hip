@@ -53,19 +53,6 @@ struct MlpParams {
   const bf16_t* hp_in;
 };
 
-// GELU by table: the mixer is VALU bound on its activation (SQ counters of 64->128->32: 70 % VALU busy, v_exp_f32 and
-// v_rcp_f32 are about 60 % of it).  1024 segments of [-8, 8): y = a_i + b_i * x with (a_i, b_i) from the exact erf GELU
-// in double precision -> |error| <= 2.4e-5 (h^2/8 * max f''), the class of `gelu_fast`; outside the range the end
-// segments extend linearly (slopes 0 and 1 to 1e-14).  One fma + clamp + cvt + ds_read_b64 + fma per element.
-constexpr int GELU_LUT_N = 1024;
-__device__ float2 g_gelu_lut[GELU_LUT_N];
-
-__device__ __forceinline__ float gelu_lut(const float2* __restrict__ tab, float x) {
-  const float t = fminf(fmaxf(fmaf(x, 64.0f, 512.0f), 0.0f), (float)(GELU_LUT_N - 1));
-  const float2 ab = tab[(int)t];
-  return fmaf(ab.y, x, ab.x);
-}
-
 // Occupancy hint: with a bare __launch_bounds__(256) hipcc budgets for one wave per SIMD and spends registers freely
 // (176 VGPRs for 128->256->64, i.e. 2 waves/SIMD); the waves of this kernel spend > 40 % of their life waiting on
 // loads (SQ_WAIT_ANY), so the kernels are compiled for the occupancy their live state allows (no spills).
@@ -75,8 +62,8 @@ constexpr int mlp_waves_per_simd(int ks, int mo, int nt) {
   return regs <= 64 ? 4 : (regs <= 112 ? 3 : (regs <= 200 ? 2 : 1));
 }
 
-// GELU_MODE: 0 = erf (A&S 7.1.26), 1 = sigmoid-form minimax (gelu_fast), 2 = table, 3 = packed fp16 polynomial (gelu_h2;
-// the projection then runs on v_mfma_f32_16x16x32_f16 with the fp16 image of W3)
+// GELU_MODE: 1 = sigmoid-form minimax (gelu_fast), 3 = packed fp16 polynomial (gelu_h2; the projection then runs on
+// v_mfma_f32_16x16x32_f16 with the fp16 image of W3)
 // HEAD: the network's 1x1x1 output projection rides in the epilogue of the LAST mixer (C_out = 32): the block output is
 // rounded to bf16 exactly as the un-fused path stores it, is itself the B fragment of one more 16x16x32 MFMA against the head
 // weights (rows beyond n_head are zero), whose result lanes write the fp32 logits; the 64 B / voxel of
@@ -95,14 +82,7 @@ pw_mlp_kernel(MlpParams p) {
   static_assert(MO % 2 == 0, "C_out must be a multiple of 32");
   static_assert(!STEMRES || (MO == 2 && (MO / 2) * NT <= 4), "the stem-recomputing residual covers C_out = 32");
   static_assert(!HEAD || MO == 2, "the fused head covers C_out = 32");
-  __shared__ __attribute__((aligned(16))) float2 lut[GELU_MODE == 2 ? GELU_LUT_N : 1];
-  if constexpr (GELU_MODE == 2) {
-    const uint4* src = reinterpret_cast<const uint4*>(g_gelu_lut);
-    uint4* dst = reinterpret_cast<uint4*>(lut);
-    dst[threadIdx.x] = src[threadIdx.x];
-    dst[threadIdx.x + 256] = src[threadIdx.x + 256];
-    __syncthreads();
-  }
+  static_assert(GELU_MODE == 1 || GELU_MODE == 3, "sigmoid-form or packed-fp16 GELU");
   constexpr bool PREFETCH_RES = (MO / 2) * NT <= 4;   // residual rows ride along with the input loads
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = blockIdx.y;
@@ -266,8 +246,8 @@ pw_mlp_kernel(MlpParams p) {
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        g[j] = GELU_MODE == 2 ? gelu_lut(lut, acc1[0][nt][j]) : (GELU_MODE == 1 ? gelu_fast(acc1[0][nt][j]) : gelu_erf(acc1[0][nt][j]));
-        g[4 + j] = GELU_MODE == 2 ? gelu_lut(lut, acc1[1][nt][j]) : (GELU_MODE == 1 ? gelu_fast(acc1[1][nt][j]) : gelu_erf(acc1[1][nt][j]));
+        g[j] = gelu_fast(acc1[0][nt][j]);
+        g[4 + j] = gelu_fast(acc1[1][nt][j]);
       }
       bh[nt] = Mma<bf16_t>::from_floats(g);
     }
@@ -581,17 +561,17 @@ pw_mlp_dma_kernel(MlpParams p, int waves_per_sample) {
 // which launches take the DMA form: level-0 width, per-sample operands, fp16 projection image, a launch of at least `mlp_dma_rows` rows
 static bool mlp_dma_applies(const pytc_mlp_args* a, const MlpParams& p) {
   return a->per_sample && p.w3_f16 && a->C_in == 32 && a->C_out == 32 && (p.HC == 2 || p.HC == 3 || p.HC == 4) &&
-         (a->res_mode == PYTC_RES_NONE || a->res_mode == PYTC_RES_ADD) && tuning_get("mlp_dma", 1) != 0 &&
-         (long)a->N * a->rows_per_sample >= (long)tuning_get("mlp_dma_rows", 1 << 20);
+         (a->res_mode == PYTC_RES_NONE || a->res_mode == PYTC_RES_ADD) && tuning_get(K_mlp_dma) != 0 &&
+         (long)a->N * a->rows_per_sample >= (long)tuning_get(K_mlp_dma_rows);
 }
 template <int KIND>
 static void mlp_dma_launch(const pytc_mlp_args* a, const MlpParams& p, hipStream_t s) {
   const long tiles = (a->rows_per_sample + 63) / 64;
   // workgroups of the launch per sample: several waves' worth per CU slot (3 workgroups per CU by LDS); every wave gets >= 2 tiles
-  long wgs = ((long)tuning_get("mlp_dma_grid", 3072) + a->N - 1) / a->N;
+  long wgs = (3072 + a->N - 1) / a->N;
   const long most = (tiles / 2 + 3) / 4;
   if (wgs > most) wgs = most < 1 ? 1 : most;
-  if (const int forced = tuning_get("mlp_dma_wgs", 0); forced > 0) wgs = forced;
+  if (const int forced = tuning_get(K_mlp_dma_wgs); forced > 0) wgs = forced;
   dim3 grid((unsigned)wgs, (unsigned)a->N), block(256);
   const int wps = (int)(wgs * 4);
   if (p.HC == 2) hipLaunchKernelGGL((pw_mlp_dma_kernel<2, KIND>), grid, block, 0, s, p, wps);
@@ -810,23 +790,6 @@ groupnorm_fold_mlp_kernel(const float* __restrict__ stats, int slots, float coun
   }
 }
 
-// one-time upload of the GELU table (host double precision; blocking copy, first mixer launch of the process)
-static bool ensure_gelu_lut() {
-  static int state = 0;     // 0 = not tried, 1 = ready, -1 = failed
-  if (state == 0) {
-    static float2 host[GELU_LUT_N];
-    auto f = [](double x) { return 0.5 * x * (1.0 + erf(x * 0.70710678118654752440)); };
-    for (int i = 0; i < GELU_LUT_N; ++i) {
-      const double x0 = -8.0 + i / 64.0, x1 = x0 + 1.0 / 64.0;
-      const double b = (f(x1) - f(x0)) * 64.0;
-      host[i].x = (float)(f(x0) - b * x0);
-      host[i].y = (float)b;
-    }
-    state = hipMemcpyToSymbol(HIP_SYMBOL(g_gelu_lut), host, sizeof(host)) == hipSuccess ? 1 : -1;
-  }
-  return state == 1;
-}
-
 template <int KS_IN, int MO, int NT>
 static void launch_mlp(const MlpParams& p, int N, hipStream_t s) {
   long rows_per_block = 4L * NT * 16;
@@ -840,32 +803,20 @@ static void launch_mlp(const MlpParams& p, int N, hipStream_t s) {
     else hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 1, false, false, true>), grid, block, 0, s, p);
     return;
   }
-  if (p.w3_f16) {
-    hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 3>), grid, block, 0, s, p);
-    return;
-  }
-  if (tuning_get("mlp_exact_gelu", 0))
-    hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 0>), grid, block, 0, s, p);
-  else if (tuning_get("mlp_gelu_lut", 0) && ensure_gelu_lut())
-    hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 2>), grid, block, 0, s, p);
-  else
-    hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 1>), grid, block, 0, s, p);
+  if (p.w3_f16) hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 3>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((pw_mlp_kernel<KS_IN, MO, NT, 1>), grid, block, 0, s, p);
 }
 
 // (C_in/32, C_out/16) pairs that occur in MedNeXt with 32 base channels: same-res, down (x2), up (/2)
 static bool dispatch_mlp(const MlpParams& p, int N, hipStream_t s) {
   const int ks = p.C_in / 32, mo = p.C_out / 16;
-  const int variant = tuning_get("mlp_variant", 0);
 #define PYTC_MLP_CASE(KS, MOO, NTT) \
   if (ks == KS && mo == MOO) { launch_mlp<KS, MOO, NTT>(p, N, s); return true; }
   // voxel tiles per wave (NT) chosen per shape from tools/kbench.py measurements on MI355X
-  if (!(variant & 1)) { PYTC_MLP_CASE(2, 4, 2) }
-  if (variant & 2) { PYTC_MLP_CASE(1, 2, 2) PYTC_MLP_CASE(2, 2, 2) }
-  if (variant & 4) { PYTC_MLP_CASE(1, 4, 2) }
   PYTC_MLP_CASE(1, 2, 4)
   PYTC_MLP_CASE(1, 4, 4)
   PYTC_MLP_CASE(2, 2, 4)
-  PYTC_MLP_CASE(2, 4, 4)
+  PYTC_MLP_CASE(2, 4, 2)
   PYTC_MLP_CASE(2, 8, 2)
   PYTC_MLP_CASE(4, 4, 2)
   PYTC_MLP_CASE(4, 8, 2)
@@ -961,13 +912,12 @@ extern "C" int pytc_pw_mlp_head_fwd(const pytc_mlp_args* a, const void* head_w, 
   p.w2_stride = (long)(a->C_hid / 16) * (a->C_in / 32) * 64;
   p.e.res = a->res; p.e.res_low = nullptr; p.e.res_bias = nullptr; p.e.y = a->y;
   p.e.rps_out = a->rows_per_sample; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode;
-  p.e.nt = stream_nt_policy((long)a->N * a->rows_per_sample * (a->C_in > a->C_out ? a->C_in : a->C_out) * 2);
+  p.e.nt = 0;
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   p.head_w = (const bf16x8_t*)head_w; p.head_b = head_b; p.head_y = head_y; p.n_head = n_head; p.store_y = store_y;
   p.w3_f16 = a->w3_format == PYTC_W3_F16 ? 1 : 0;
   dim3 grid((unsigned)((p.rps + 4L * 4 * 16 - 1) / (4L * 4 * 16)), (unsigned)a->N), block(256);
   hipStream_t s = (hipStream_t)stream;
-  const bool exact = tuning_get("mlp_exact_gelu", 0) != 0;
   if (mlp_dma_applies(a, p)) {
     mlp_dma_launch<2>(a, p, s);
     PYTC_LAUNCH_CHECK("pw_mlp_head_dma");
@@ -977,11 +927,9 @@ extern "C" int pytc_pw_mlp_head_fwd(const pytc_mlp_args* a, const void* head_w, 
     if (a->C_in == 32) hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 3, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((pw_mlp_kernel<2, 2, 4, 3, true>), grid, block, 0, s, p);
   } else if (a->C_in == 32) {
-    if (exact) hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 0, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 1, true>), grid, block, 0, s, p);
+    hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 1, true>), grid, block, 0, s, p);
   } else {
-    if (exact) hipLaunchKernelGGL((pw_mlp_kernel<2, 2, 4, 0, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((pw_mlp_kernel<2, 2, 4, 1, true>), grid, block, 0, s, p);
+    hipLaunchKernelGGL((pw_mlp_kernel<2, 2, 4, 1, true>), grid, block, 0, s, p);
   }
   PYTC_LAUNCH_CHECK("pw_mlp_head");
   return PYTC_OK;
@@ -1005,7 +953,7 @@ extern "C" int pytc_pw_mlp_stemres_fwd(const pytc_mlp_args* a, const float* stem
   p.e.res = a->y;              // never dereferenced (the residual rows are recomputed); non-null for the epilogue's checks
   p.e.y = a->y;
   p.e.rps_out = a->rows_per_sample; p.e.C_out = a->C_out; p.e.res_mode = PYTC_RES_ADD;
-  p.e.nt = stream_nt_policy((long)a->N * a->rows_per_sample * (a->C_in > a->C_out ? a->C_in : a->C_out) * 2);
+  p.e.nt = 0;
   p.stem_x = stem_x; p.stem_w = stem_w; p.stem_b = stem_b;
   p.w3_f16 = a->w3_format == PYTC_W3_F16 ? 1 : 0;
   dim3 grid((unsigned)((p.rps + 4L * 4 * 16 - 1) / (4L * 4 * 16)), (unsigned)a->N), block(256);
@@ -1018,7 +966,6 @@ extern "C" int pytc_pw_mlp_stemres_fwd(const pytc_mlp_args* a, const float* stem
     return PYTC_OK;
   }
   if (p.w3_f16) hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 3, false, true>), grid, block, 0, s, p);
-  else if (tuning_get("mlp_exact_gelu", 0) != 0) hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 0, false, true>), grid, block, 0, s, p);
   else hipLaunchKernelGGL((pw_mlp_kernel<1, 2, 4, 1, false, true>), grid, block, 0, s, p);
   PYTC_LAUNCH_CHECK("pw_mlp_stemres");
   return PYTC_OK;
@@ -1109,7 +1056,7 @@ static int mlp_fwd_impl(const pytc_mlp_args* a, void* hp, void* stream, const vo
   p.w2_stride = (long)(a->C_hid / 16) * (a->C_in / 32) * 64;
   p.e.res = a->res; p.e.res_low = a->res_low; p.e.res_bias = a->res_bias; p.e.y = a->y;
   p.e.rps_out = a->rows_per_sample; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode;
-  p.e.nt = stream_nt_policy((long)a->N * a->rows_per_sample * (a->C_in > a->C_out ? a->C_in : a->C_out) * 2);
+  p.e.nt = 0;
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   p.hp = (bf16_t*)hp;
   p.hp_in = (const bf16_t*)hp_in;

@@ -272,7 +272,7 @@ extern "C" int pytc_pw_mlp_lds_fwd(const pytc_mlp_args* a, void* stream) {
   p.w2_stride = (long)(a->C_hid / 16) * (a->C_in / 32) * 64;
   p.e.res = a->res; p.e.res_low = a->res_low; p.e.res_bias = a->res_bias; p.e.y = a->y;
   p.e.rps_out = a->rows_per_sample; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode;
-  p.e.nt = stream_nt_policy((long)a->N * a->rows_per_sample * (a->C_in > a->C_out ? a->C_in : a->C_out) * 2);
+  p.e.nt = 0;
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   if (a->res_mode == PYTC_RES_UPSAMPLE) {
     PYTC_REQUIRE((long)a->Di * a->Hi * a->Wi == a->rows_per_sample && !(a->Di & 1) && !(a->Hi & 1) && !(a->Wi & 1) &&
@@ -282,7 +282,7 @@ extern "C" int pytc_pw_mlp_lds_fwd(const pytc_mlp_args* a, void* stream) {
   }
   hipStream_t s = (hipStream_t)stream;
   const int ks = a->C_in / 32, mo = a->C_out / 16;
-  const int variant = tuning_get("mlp_lds_variant", 0);
+  const int variant = tuning_get(K_mlp_lds_variant);
   if (ks == 2 && mo == 2) launch_mlp_lds<2, 2, 2>(p, variant, s);     // 64 rows per wave (NT = 4): 748 us at best against 735
   else if (ks == 2 && mo == 4) launch_mlp_lds<2, 4, 2>(p, variant, s);
   else if (ks == 4 && mo == 4) launch_mlp_lds<4, 4, 2>(p, variant, s);

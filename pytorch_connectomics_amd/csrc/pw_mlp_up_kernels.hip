@@ -70,7 +70,7 @@ constexpr UpStep up_step(int pz, int s) {
 
 // One tile with the output z parity PZ known at compile time: the tap sets and the neighbour set are static, so the
 // prologue is straight-line code (with a run-time parity hipcc keeps both variants' values live and spills ~70 registers).
-template <int KS_IN, int MO, int GELU_MODE, int PZ>
+template <int KS_IN, int MO, int PZ>
 __device__ __forceinline__ void up_tile(const MlpUpParams& p, const float* wl, int n, int mz, int my, int xs, int lane) {
   constexpr int NT = 4;
   constexpr int pz = PZ;
@@ -219,8 +219,8 @@ __device__ __forceinline__ void up_tile(const MlpUpParams& p, const float* wl, i
       float g[8];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        g[j] = GELU_MODE == 1 ? gelu_fast(acc1[0][nt][j]) : gelu_erf(acc1[0][nt][j]);
-        g[4 + j] = GELU_MODE == 1 ? gelu_fast(acc1[1][nt][j]) : gelu_erf(acc1[1][nt][j]);
+        g[j] = gelu_fast(acc1[0][nt][j]);
+        g[4 + j] = gelu_fast(acc1[1][nt][j]);
       }
       bh[nt] = Mma<bf16_t>::from_floats(g);
     }
@@ -268,7 +268,7 @@ __device__ __forceinline__ void up_tile(const MlpUpParams& p, const float* wl, i
   }
 }
 
-template <int KS_IN, int MO, int GELU_MODE>
+template <int KS_IN, int MO>
 __global__ void __launch_bounds__(256, up_waves_per_simd(KS_IN, MO))
 pw_mlp_up_kernel(MlpUpParams p) {
   static_assert(MO % 2 == 0, "C_out must be a multiple of 32");
@@ -285,16 +285,15 @@ pw_mlp_up_kernel(MlpUpParams p) {
   const int pz = tq & 1; tq >>= 1;
   const int mz = tq % p.D;
   const int n = tq / p.D;
-  if (pz) up_tile<KS_IN, MO, GELU_MODE, 1>(p, wl, n, mz, my, xs, lane);
-  else up_tile<KS_IN, MO, GELU_MODE, 0>(p, wl, n, mz, my, xs, lane);
+  if (pz) up_tile<KS_IN, MO, 1>(p, wl, n, mz, my, xs, lane);
+  else up_tile<KS_IN, MO, 0>(p, wl, n, mz, my, xs, lane);
 }
 
 template <int KS_IN, int MO>
 static void launch_up(const MlpUpParams& p, hipStream_t s) {
   dim3 grid((unsigned)((p.tiles + 3) / 4)), block(256);
   const size_t lds = (size_t)27 * p.C_in * sizeof(float);
-  if (tuning_get("mlp_exact_gelu", 0)) hipLaunchKernelGGL((pw_mlp_up_kernel<KS_IN, MO, 0>), grid, block, lds, s, p);
-  else hipLaunchKernelGGL((pw_mlp_up_kernel<KS_IN, MO, 1>), grid, block, lds, s, p);
+  hipLaunchKernelGGL((pw_mlp_up_kernel<KS_IN, MO>), grid, block, lds, s, p);
 }
 
 }  // namespace pytc

@@ -25,7 +25,6 @@ constexpr int WAVE = 64;
 // ---- last-error plumbing (thread local; the ABI returns an int status) -----------------
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
-int tuning_get(const char* key, int dflt);
 bool ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what);   // per (kernel, device) opt-in above 64 KB of dynamic LDS
 bool take_launch_failure();   // a launch helper gave up before launching (error string set): PYTC_LAUNCH_CHECK turns it into a status
 
@@ -43,6 +42,41 @@ bool take_launch_failure();   // a launch helper gave up before launching (error
     hipError_t e_ = hipGetLastError();                           \
     if (e_ != hipSuccess) return pytc::hip_fail(e_, name);       \
   } while (0)
+
+// ---- tuning knobs: the CLOSED set of keys pytc_set_tuning / PYTC_TUNING accept, one row each: name, default, meaning.  Every knob
+// selects the kernel form an A/B parity test compares against the default (tests/); a row is the only place a default is written.
+#define PYTC_KNOBS(X)                                                                                                             \
+  X(channel_act_flat, 1, "channel activation of contiguous NDHWC tensors as a flat 16-byte stream; 0 = the per-voxel kernel")      \
+  X(conv_wgrad_mfma, 1, "dense-conv weight gradient on the matrix cores (bf16); 0 = the VALU kernel")                              \
+  X(dw_wgrad_march, 1, "depthwise K = 3 / stride 1 weight gradient as a z-march; 0 = the vector / generic kernels")                \
+  X(dw_wgrad_vec, 1, "depthwise K = 3 weight gradient with 16-byte channel vectors; 0 = the generic kernel")                       \
+  X(dwconvT_tile, 1, "transposed depthwise conv at C = 64 / 128 (bf16) as one tile of input cells per workgroup; 0 = cell kernel") \
+  X(dwconv_march_h16, 1, "VALU z-march depthwise conv: packed-f16 in-plane partial sums; 0 = fp32 taps")                           \
+  X(dwconv_mfma, 1, "bf16 stride-1 K = 3 depthwise forward (and the fused block) on the matrix cores; 0 = the VALU z-march")       \
+  X(dwconv_mfma_variant, 0, "matrix-core depthwise conv: bit 0 = hi + lo weight halves, bit 1 = two planes in flight, not three")  \
+  X(dwconv_s2_march, 1, "stride-2 K = 3 depthwise conv at C = 32 / 64 (bf16) as a z-march over an LDS ring; 0 = gather kernel")    \
+  X(elementwise_vec, 1, "16-byte vector forms of the norm-apply / elementwise training kernels; 0 = the scalar kernels")           \
+  X(mixer_bwd_rc_slot_div, 1, "recomputing mixer backward: divide the slot count (fewer, longer slots)")                           \
+  X(mlp_chunk_variant, 0, "chunked-hidden mixer (pw_mlp_chunk_kernels.hip): tile shape of the launch")                             \
+  X(mlp_dma, 1, "level-0 mixer with DMA-prefetched row tiles (pw_mlp_dma_kernel); 0 = one tile per wave")                          \
+  X(mlp_dma_rows, 1 << 20, "fewest rows of a launch that takes the DMA mixer")                                                     \
+  X(mlp_dma_wgs, 0, "DMA mixer: workgroups per sample; 0 = chosen from the row count")                                             \
+  X(mlp_lds_variant, 0, "LDS-resident mixer (pw_mlp_lds_kernels.hip): tile shape of the launch")                                   \
+  X(norm_bwd_from_wgrad_flat, 1, "GroupNorm-backward epilogue of the expand weight gradient as one flat kernel; 0 = chunked")      \
+  X(pw_gemm_rows, 0, "LDS-tiled 1x1 GEMM: 64 / 128 forces the rows per workgroup; 0 = by problem size")                            \
+  X(pw_thin, 1, "plain 1x1 convs with one input / few output channels on the thin kernels; 0 = the generic kernel")                \
+  X(wgrad_dgrad_fused, 1, "projecting conv's weight gradient and the GELU-backward data gradient in one kernel; 0 = two launches")  \
+  X(wgrad_small_split, 1, "matrix-core 1x1 weight gradient: more, shorter row slots when the launch would leave CUs idle")         \
+  X(wgrad_valu, 0, "1: 1x1 weight gradient on the VALU kernel instead of the matrix cores")                                        \
+  X(wgrad_whole_rounds, 1, "matrix-core 1x1 weight gradient: round the slot count down to whole rounds of resident workgroups")
+
+enum Knob {
+#define PYTC_KNOB_ENUM(name, dflt, doc) K_##name,
+  PYTC_KNOBS(PYTC_KNOB_ENUM)
+#undef PYTC_KNOB_ENUM
+  K_COUNT
+};
+int tuning_get(Knob k);      // current value; an unregistered key does not compile
 
 // ---- element traits: T in {float, bf16_t}; vectors of VEC channels --------------------
 template <typename T, int VEC>

@@ -785,8 +785,7 @@ using namespace pytc;
 struct CwPlan { bool mfma, rag_o, rag_k; int mt, nt, kp, tiles, slots; long per_slot; };
 // one input and one output channel, 3^3 taps (the last conv of a single-class U-Net): a 27-bin correlation of two scalar fields
 static bool cw_scalar(int C_in, int C_out, const int32_t* k, int dtype) {
-  return C_in == 1 && C_out == 1 && k[0] == 3 && k[1] == 3 && k[2] == 3 && (dtype == PYTC_BF16 || dtype == PYTC_F32) &&
-         tuning_get("conv_wgrad_scalar", 1) != 0;
+  return C_in == 1 && C_out == 1 && k[0] == 3 && k[1] == 3 && k[2] == 3 && (dtype == PYTC_BF16 || dtype == PYTC_F32);
 }
 
 static CwPlan cw_plan(int N, int D, int H, int W, int C_in, int C_out, const int32_t* k, int dtype) {
@@ -804,7 +803,7 @@ static CwPlan cw_plan(int N, int D, int H, int W, int C_in, int C_out, const int
   // rows must be 16-byte aligned (C % 8 == 0); a channel count that is not a multiple of the tile width leaves the last tile
   // partly filled (24 = 16 + 8, 40 = 16 + 16 + 8: RSUNet's stock widths [18, 36, ...] padded to 8 by the model)
   p.mfma = dtype == PYTC_BF16 && k[1] == k[2] && (k[1] == 3 || k[1] == 1) && (p.rag_o || C_out % 8 == 0) &&
-           (p.rag_k || C_in % 8 == 0) && (tuning_get("conv_wgrad_mfma", 1) != 0);
+           (p.rag_k || C_in % 8 == 0) && (tuning_get(K_conv_wgrad_mfma) != 0);
   if (p.mfma) {
     p.mt = (!p.rag_o && C_out % 32 == 0) ? 2 : 1;
     p.nt = (!p.rag_k && C_in % 32 == 0) ? 2 : 1;
@@ -930,7 +929,7 @@ extern "C" int pytc_act_bwd(const void* da, const void* x, const float* ab, void
   hipStream_t s = (hipStream_t)stream;
   {
     const int vec = dtype == PYTC_BF16 ? 8 : 4;
-    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get("elementwise_vec", 1)) {
+    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
       const long chunks = total / vec;
       if (dtype == PYTC_BF16)
         hipLaunchKernelGGL(act_bwd_vec_kernel<bf16_t>, dim3(grid_for(chunks)), dim3(256), 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, (bf16_t*)dt, (bf16_t*)dp, (long)rows, C, chunks, act, prm);
@@ -955,7 +954,7 @@ extern "C" int pytc_norm_bwd_apply_general(const void* d, const void* x, const f
   hipStream_t s = (hipStream_t)stream;
   {
     const int vec = dtype == PYTC_BF16 ? 8 : 4;
-    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get("elementwise_vec", 1)) {
+    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
       const long chunks = total / vec;
       if (dtype == PYTC_BF16)
         hipLaunchKernelGGL(norm_bwd_apply_general_vec_kernel<bf16_t>, dim3(grid_for(chunks)), dim3(256), 0, s, (const bf16_t*)d, (const bf16_t*)x, mean_rstd, gamma, M, (bf16_t*)dx, (long)rows, C, chunks);

@@ -201,6 +201,8 @@ stem_pack_mfma_kernel(const float* __restrict__ wx, const float* __restrict__ wb
   }
 }
 
+// STORE_PERMUTE is always true (the lane permutation before the store; the plain order lost and is gone).  The parameter stays for
+// now: as a plain function the kernel compiles to different code (register allocation, 1007 -> 1010 instructions)
 template <bool STORE_PERMUTE>
 __global__ void __launch_bounds__(256, 4)
 stem_dwconv_k3_mfma_kernel(const float* __restrict__ x, const h8_t* __restrict__ frag, const float* __restrict__ kc,
@@ -380,7 +382,7 @@ static int sd_vx(int) { return 4; }
 static int sd_it() { return SD_IT; }
 
 static bool sd_mfma(int D, int H, int W) {
-  return W % SM_XT == 0 && H % SM_YT == 0 && D % SM_ZT == 0 && tuning_get("stem_mfma", 1) != 0;
+  return W % SM_XT == 0 && H % SM_YT == 0 && D % SM_ZT == 0;
 }
 
 // z extent per workgroup: the largest of 32 / 16 / 8 planes that still yields >= 256 workgroups for ONE sample.  A function of
@@ -390,12 +392,9 @@ static void sd_geom(pytc::StemMf& m, int D, int H, int W) {
   m.D = D; m.H = H; m.W = W;
   m.bx = W / SM_XT;
   m.by = (H + SM_YT - 1) / SM_YT;
-  const int forced = tuning_get("stem_mfma_zr", 0);
   m.zr = SM_ZT;
-  if (forced >= SM_ZT && forced % SM_ZT == 0) m.zr = forced;
-  else
-    for (int zr = 32; zr > SM_ZT; zr >>= 1)
-      if ((long)m.bx * m.by * ((D + zr - 1) / zr) >= 256) { m.zr = zr; break; }
+  for (int zr = 32; zr > SM_ZT; zr >>= 1)
+    if ((long)m.bx * m.by * ((D + zr - 1) / zr) >= 256) { m.zr = zr; break; }
   m.bz = (D + m.zr - 1) / m.zr;
 }
 
@@ -433,12 +432,8 @@ extern "C" int pytc_stem_dwconv3d_fwd(const float* x, const float* wx, const flo
     StemMf m;
     sd_geom(m, D, H, W);
     const float* kc = (const float*)((const char*)mfma_image + SM_IMG_FRAG * 16);
-    if (tuning_get("stem_store_permute", 1))
-      hipLaunchKernelGGL(stem_dwconv_k3_mfma_kernel<true>, dim3(slots, N), dim3(256), 0, (hipStream_t)stream, x,
-                         (const h8_t*)mfma_image, kc, (bf16_t*)y, stats, m, slots);
-    else
-      hipLaunchKernelGGL(stem_dwconv_k3_mfma_kernel<false>, dim3(slots, N), dim3(256), 0, (hipStream_t)stream, x,
-                         (const h8_t*)mfma_image, kc, (bf16_t*)y, stats, m, slots);
+    hipLaunchKernelGGL(stem_dwconv_k3_mfma_kernel<true>, dim3(slots, N), dim3(256), 0, (hipStream_t)stream, x,
+                       (const h8_t*)mfma_image, kc, (bf16_t*)y, stats, m, slots);
     PYTC_LAUNCH_CHECK("stem_dwconv3d_mfma");
     return PYTC_OK;
   }

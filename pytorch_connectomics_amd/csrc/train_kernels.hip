@@ -421,7 +421,7 @@ struct MixBwd {
   bf16_t* dhp;              // [N][rows][C_hid]
   long rows_per_sample, rows_per_slot;
   int sps, want_db3;
-  int probe;                // measurements only (wrong results): 1 = identity in the place of the activation and its derivative
+  int probe;                // every launch passes 0 (1 = identity in the place of the activation and its derivative)
 };
 
 template <int HT, bool GN>
@@ -1046,7 +1046,7 @@ reduce_slots_batched_kernel(const float* __restrict__ part, float* __restrict__ 
 struct DwWg {
   int N, Dg, Hg, Wg, Dx, Hx, Wx, C, K, stride, pad;
   int lpv, vs, iters, slots;
-  int kz_inner = 0;       // dw_wgrad_vec_kernel: kz as the fastest index of an XCD-aware 1-D grid
+  int kz_inner = 0;       // dw_wgrad_vec_kernel: kz as the fastest index of an XCD-aware 1-D grid (its launch always sets 1)
 };
 
 template <typename T, int VEC, int K>
@@ -1507,7 +1507,7 @@ norm_bwd_from_wgrad_flat_kernel(float* __restrict__ M, const float* __restrict__
 
 static void launch_norm_bwd_from_wgrad(dim3 grid, hipStream_t s, float* M, const float* dbp, float* q, const float* W2, const float* gamma,
                                        const float* ab, const float* mr, float* s_out, float* coef, int N, int C, int H, int sps, float inv_count) {
-  if (H <= NBW_HMAX && tuning_get("norm_bwd_from_wgrad_flat", 1))
+  if (H <= NBW_HMAX && tuning_get(K_norm_bwd_from_wgrad_flat))
     hipLaunchKernelGGL(norm_bwd_from_wgrad_flat_kernel, grid, dim3(256), 0, s, M, dbp, q, W2, gamma, ab, mr, s_out, coef, N, C, H, sps, inv_count);
   else
     hipLaunchKernelGGL(norm_bwd_from_wgrad_kernel, grid, dim3(256), 0, s, M, dbp, q, W2, gamma, ab, mr, s_out, coef, N, C, H, sps, inv_count);
@@ -1695,11 +1695,11 @@ static int wgrad_mfma_slots(long rows_total, int C_in, int C_out, int slots) {
   // third full.  Cut it to whole rounds of resident workgroups (the slot count only groups rows: sums stay in slot order)
   const int per_cu = mt * nt >= 8 ? 2 : (mt * nt >= 4 ? 3 : 4);
   const long resident = 256L * per_cu / tiles;
-  if (tuning_get("wgrad_whole_rounds", 1) && resident >= 8 && want > resident) want = (want / resident) * resident;
+  if (tuning_get(K_wgrad_whole_rounds) && resident >= 8 && want > resident) want = (want / resident) * resident;
   // deep levels (14^3 / 7^3 voxels per sample): 2048-row slots leave 160 / 128 workgroups, each a chain of 11-17 dependent
   // row blocks per wave (42-48 us for 17 / 4 MB of operands).  Up to ~2 workgroups per CU, slots shrink to >= 256 rows
   // (2 row blocks per wave: what the two-deep prefetch needs); the extra partials are a few MB
-  if (tuning_get("wgrad_small_split", 1) && want * tiles < 512) {
+  if (tuning_get(K_wgrad_small_split) && want * tiles < 512) {
     long more = 512 / tiles, most = rows_total / 256;
     more = more < most ? more : most;
     if (more > want) want = more;
@@ -1735,7 +1735,7 @@ static int pw_wgrad_impl(const void* x, const float* ab, const void* dy, float* 
   float* dWp = workspace;
   float* dbp = workspace + (long)slots * C_out * C_in;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == PYTC_BF16 && mt && nt && tuning_get("wgrad_valu", 0) == 0) {
+  if (dtype == PYTC_BF16 && mt && nt && tuning_get(K_wgrad_valu) == 0) {
     // bf16, channel counts in multiples of 16: MFMA path (transpose reads from a wave-private LDS image)
     dim3 grid(slots, (C_out / (16 * mt)) * (C_in / (16 * nt)));
     const bf16_t* xp = (const bf16_t*)x;
@@ -1782,8 +1782,8 @@ extern "C" int pytc_pw_wgrad_partial(const void* x, const float* ab, const void*
 }
 
 extern "C" int pytc_pw_wgrad_dgrad_supported(int C_in, int C_out, int dtype) {
-  return (dtype == PYTC_BF16 && C_out == 32 && (C_in == 64 || C_in == 32 || (C_in == 128 && tuning_get("wgrad_dgrad_wide", 1) != 0)) &&
-          tuning_get("wgrad_dgrad_fused", 1) != 0) ? 1 : 0;
+  return (dtype == PYTC_BF16 && C_out == 32 && (C_in == 64 || C_in == 32 || C_in == 128) &&
+          tuning_get(K_wgrad_dgrad_fused) != 0) ? 1 : 0;
 }
 
 extern "C" int pytc_pw_wgrad_dgrad_partial(const void* x, const void* dy, const void* w_t_paired, void* dx, float* workspace,
@@ -1891,15 +1891,15 @@ extern "C" int pytc_pw_wgrad_groupnorm(const void* t, const float* mean_rstd, co
    returns.  workspace (pytc_mixer_bwd_rc_ws_elems floats), S = N * sps slots:
      dW3 partials [S][32][C_hid] | db3 partials [S][32] | gn: M partials [S][C_hid][32] | q partials [S][C_hid] | term [N][C_hid][32] | q [N][C_hid] */
 extern "C" int pytc_mixer_bwd_rc_supported(int C, int C_hid, int C_out, int dtype) {      // 0 no, 1 without the GroupNorm form, 2 both
-  if (!(dtype == PYTC_BF16 && C == 32 && C_out == 32 && (C_hid == 64 || C_hid == 32 || C_hid == 96)) || tuning_get("mixer_bwd_rc", 1) == 0) return 0;
-  return (C_hid == 96 || tuning_get("mixer_bwd_rc_gn", 1) == 0) ? 1 : 2;          // 96: the GroupNorm form's accumulators do not fit 256 registers (68 spilled)
+  if (!(dtype == PYTC_BF16 && C == 32 && C_out == 32 && (C_hid == 64 || C_hid == 32 || C_hid == 96))) return 0;
+  return C_hid == 96 ? 1 : 2;          // 96: the GroupNorm form's accumulators do not fit 256 registers (68 spilled)
 }
 
 extern "C" int pytc_mixer_bwd_rc_sps(int N, int64_t rows_per_sample, int C_hid) {
   const long rows_total = (long)N * rows_per_sample;
   int slots = wgrad_mfma_slots(rows_total, C_hid, 32, pytc_pw_wgrad_slots(rows_total));
   // knob (measurement): fewer, longer slots -- halves the partials the block's reduction launch reads
-  const int div = tuning_get("mixer_bwd_rc_slot_div", 1);
+  const int div = tuning_get(K_mixer_bwd_rc_slot_div);
   if (div > 1 && slots / div >= 512) slots /= div;
   const int sps = slots / N;
   return sps < 1 ? 1 : sps;
@@ -1937,7 +1937,7 @@ extern "C" int pytc_mixer_bwd_rc(const void* t, const float* ab, const float* me
   float* qv = term + (long)N * per;
   q.dhp = (bf16_t*)dhp;
   q.rows_per_sample = rows_per_sample; q.rows_per_slot = (rows_per_sample + sps - 1) / sps;
-  q.sps = sps; q.want_db3 = want_db3; q.probe = tuning_get("mixer_bwd_rc_probe", 0);
+  q.sps = sps; q.want_db3 = want_db3; q.probe = 0;
   hipStream_t s = (hipStream_t)stream;
   if (C_hid == 64) launch_mixer_bwd_rc<4>(q, gn, (int)S, s);
   else if (C_hid == 96) hipLaunchKernelGGL((mixer_bwd_rc_kernel<6, false>), dim3((unsigned)S), dim3(256), 0, s, q);
@@ -1992,7 +1992,7 @@ static int march_slots(int N, const int32_t* gd, const int32_t* xd, int C, int K
 
 static bool wg_vec_ok(int C, int K, int dtype) {
   const int epv = dtype == PYTC_BF16 ? 8 : 4;
-  return K == 3 && C % epv == 0 && C / epv <= 256 && tuning_get("dw_wgrad_vec", 1) != 0;
+  return K == 3 && C % epv == 0 && C / epv <= 256 && tuning_get(K_dw_wgrad_vec) != 0;
 }
 static void make_wg_vec(DwWg& q, long& rps, int N, const int32_t* gd, const int32_t* xd, int C, int K, int stride, int dtype) {
   q.N = N; q.Dg = gd[0]; q.Hg = gd[1]; q.Wg = gd[2]; q.Dx = xd[0]; q.Hx = xd[1]; q.Wx = xd[2];
@@ -2000,12 +2000,9 @@ static void make_wg_vec(DwWg& q, long& rps, int N, const int32_t* gd, const int3
   const int PL = 256 / (C / (dtype == PYTC_BF16 ? 8 : 4));
   const long vg = (long)q.Dg * q.Hg * q.Wg;
   // positions per lane: 16 where that still gives the chip >= 1024 workgroups, down to 4 below (a 14^3 x 256 launch had 264 workgroups whose
-  // lanes walked 16 positions, one L2 round trip each: 50 us for 11 MB; knob dw_wgrad_vec_ppl forces a value)
-  long ppl = tuning_get("dw_wgrad_vec_ppl", 0);
-  if (ppl <= 0) {
-    ppl = vg * N * 3 / ((long)PL * 1024);
-    ppl = ppl < 4 ? 4 : (ppl > 16 ? 16 : ppl);
-  }
+  // lanes walked 16 positions, one L2 round trip each: 50 us for 11 MB)
+  long ppl = vg * N * 3 / ((long)PL * 1024);
+  ppl = ppl < 4 ? 4 : (ppl > 16 ? 16 : ppl);
   long sl = (vg + (long)PL * ppl - 1) / ((long)PL * ppl);
   q.slots = (int)(sl < 1 ? 1 : (sl > 1024 ? 1024 : sl));
   rps = (vg + q.slots - 1) / q.slots;
@@ -2074,9 +2071,8 @@ static int dw_wgrad_impl(const void* g, const void* x, float* dW, float* db, flo
     float* dWv = workspace;
     float* dbv = workspace + (long)total * nWv;
     hipStream_t sv = (hipStream_t)stream;
-    q.kz_inner = tuning_get("dw_wgrad_vec_kz_inner", 1);
-    dim3 grid(q.slots, N, 3), block(256);
-    if (q.kz_inner) grid = dim3((unsigned)(q.slots * N * 3), 1, 1);
+    q.kz_inner = 1;
+    dim3 grid((unsigned)(q.slots * N * 3), 1, 1), block(256);
     DISPATCH_T(dtype,
                hipLaunchKernelGGL(dw_wgrad_vec_kernel<bf16_t>, grid, block, 0, sv, (const bf16_t*)g, (const bf16_t*)x, dWv, db ? dbv : nullptr, q, rps),
                hipLaunchKernelGGL(dw_wgrad_vec_kernel<float>, grid, block, 0, sv, (const float*)g, (const float*)x, dWv, db ? dbv : nullptr, q, rps),

@@ -340,7 +340,7 @@ extern "C" int pytc_channel_activation(float* value, int C, int64_t nvox, int ch
   PYTC_REQUIRE(value && C >= 1 && nvox > 0 && c0 >= 0 && c1 <= C && c0 < c1, "channel_activation: bad arguments");
   PYTC_REQUIRE(act == PYTC_ACT_NONE || act == PYTC_ACT_SIGMOID || act == PYTC_ACT_TANH || act == 4,
                "channel_activation: bad activation %d", act);
-  if (channels_last && act != 4 && ((long)nvox * C) % 4 == 0 && ((uintptr_t)value & 15) == 0 && tuning_get("channel_act_flat", 1)) {
+  if (channels_last && act != 4 && ((long)nvox * C) % 4 == 0 && ((uintptr_t)value & 15) == 0 && tuning_get(K_channel_act_flat)) {
     const long n4 = (long)nvox * C / 4;
     const long want = (n4 + 255) / 256;
     hipLaunchKernelGGL(channel_activation_flat_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, (hipStream_t)stream,

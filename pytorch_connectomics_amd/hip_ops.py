@@ -1849,7 +1849,7 @@ def conv3d_strided(x: torch.Tensor, w_packed: torch.Tensor, *, c_out: int, kerne
 
 
 def convT3d_phase_supported(c_out: int, c_in: int, dtype: torch.dtype) -> bool:
-    """the LDS-tiled phase form covers this stride-2 transposed gather (bf16, C_in % 8 == 0, knob convT_phase_tile)"""
+    """the LDS-tiled phase form covers this stride-2 transposed gather (bf16, C_in % 8 == 0)"""
     return dtype == torch.bfloat16 and bool(nat.lib().pytc_convT3d_phase_supported(int(c_out), int(c_in), nat.BF16))
 
 

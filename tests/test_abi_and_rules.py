@@ -82,10 +82,31 @@ def test_tuning_knobs_from_the_environment():
     good = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True,
                           env={**os.environ, "PYTC_TUNING": "dwconv_mfma=0, mlp_lds_variant=3"})
     assert good.returncode == 0 and "loaded" in good.stdout, good.stderr[-500:]
-    for bad_value in ("dwconv_mfma", "dwconv_mfma=fast", "=3"):
+    for bad_value in ("dwconv_mfma", "dwconv_mfma=fast", "=3", "no_such_knob=1"):
         bad = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True,
                              env={**os.environ, "PYTC_TUNING": bad_value})
         assert bad.returncode != 0 and "PYTC_TUNING" in bad.stderr, (bad_value, bad.stderr[-300:])
+
+
+def test_tuning_knob_registry_is_closed():
+    """Every row of the knob table (PYTC_KNOBS, csrc/pytc_common.h) can be set through pytc_set_tuning and put back to its default;
+    any other key -- a retired knob, a typo -- is refused with PYTC_ERR_INVALID and named in the last-error string."""
+    from pytorch_connectomics_amd import _native as nat
+    lib = nat.lib()
+    ERR_INVALID = 1        # PYTC_ERR_INVALID
+    table = (ROOT / "pytorch_connectomics_amd" / "csrc" / "pytc_common.h").read_text()
+    rows = re.findall(r"^\s*X\((\w+), ([^,]+), \"[^\"]+\"\)", table, flags=re.M)
+    assert rows and len(rows) == table.count("\n  X(") and len({k for k, _ in rows}) == len(rows) and "dwconv_mfma" in dict(rows), rows
+    for key, default in rows:
+        default = int(eval(default, {"__builtins__": {}}))
+        try:
+            assert lib.pytc_set_tuning(key.encode(), default + 1) == nat.OK, key
+        finally:
+            assert lib.pytc_set_tuning(key.encode(), default) == nat.OK, key
+    for key in ("mlp_exact_gelu", "dwconv_mfma_probe", "dwconv_mfmma", ""):
+        assert lib.pytc_set_tuning(key.encode(), 1) == ERR_INVALID, key
+        assert key in lib.pytc_last_error().decode()
+    assert lib.pytc_set_tuning(None, 1) == ERR_INVALID
 
 
 def test_depthwise_dispatch_table_and_batch_invariant_statistics_slots():
