@@ -29,7 +29,7 @@ extern "C" {
  * 5: pytc_cldice_* (the clDice soft skeleton and its gradient).
  * 6: the key set of pytc_set_tuning is closed: an unknown key returns PYTC_ERR_INVALID (the last error names it).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 6
+#define PYTC_ABI_VERSION 7
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -674,6 +674,14 @@ int pytc_conv3d_pack_weight_dgrad(const float* w, int C_out, int C_in, int kd, i
  * total_blocks = sum of ceil(elements / 256).  Images are bit-identical to the single-weight packs. */
 int pytc_conv3d_pack_plan(int C_out, int C_in, int kd, int kh, int kw, int dtype, int direct, int64_t* out);
 int pytc_conv3d_pack_multi(const int64_t* table_dev, int n_items, int64_t total_blocks, void* stream);
+/* pytc_conv3d_launch_plan: which kernel, in which launch form, pytc_conv3d_fwd (phase = 0) or pytc_convT3d_phase_fwd (phase = 1) runs
+ * for these arguments -- answered by the functions the launches themselves call, pure host code (no device needed).  D / H / W: the
+ * grid the kernel walks (phase = 1: the INPUT grid of the transposed conv, kernel 3).  out[0] = form (0 one-input-channel stencil,
+ * 1 LDS tile, 2 MFMA gather kernel, 3 thin-input kernel), out[1] = output-channel tiles per workgroup MT (form 0: channels per
+ * thread), out[2..4] = KC, chunks, groups per chunk of the tile plan (phase = 1: of phase 7; 0 for the other forms), out[5] =
+ * workgroups.  PYTC_ERR_UNSUPPORTED: phase = 1 and the shape has no phase plan. */
+int pytc_conv3d_launch_plan(int N, int D, int H, int W, int C_in, int C_out, int kd, int kh, int kw, int dtype, int has_pre,
+                            int has_res, int phase, int64_t* out);
 int pytc_norm_bwd_means(const float* s, const float* gamma, float* M, float* dgamma, float* dbeta, int N, int C, int groups,
                         float rows, void* stream);
 /* The two group-statistics kernels with an explicit group width (round 4): `groups` groups of `cpg` channels, and the channels from

@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 6          # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 7          # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -214,6 +214,7 @@ _SIGS = {
                                             C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "pytc_conv3d_pack_plan": (C.c_int, [C.c_int] * 7 + [C.c_void_p]),
     "pytc_conv3d_pack_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "pytc_conv3d_launch_plan": (C.c_int, [C.c_int] * 13 + [C.c_void_p]),
     "pytc_conv3d_pack_weight_dgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pytc_norm_bwd_means": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_void_p]),

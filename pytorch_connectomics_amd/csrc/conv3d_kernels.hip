@@ -272,17 +272,24 @@ conv3d_c1_stencil_kernel(const T* __restrict__ x, const T* __restrict__ wp, cons
   }
 }
 
-// -> true when the launch was made: one input channel, 3^3 taps, stride 1 ('same') or 2 (pad 1), no fused pre-activation / residual
+// -> output channels per thread (OCT) of the stencil launch, 0 when the stencil does not serve the conv: one input channel, 3^3 taps,
+// stride 1 ('same') or 2 (pad 1), no fused pre-activation / residual.  The one rule of the launch and of pytc_conv3d_launch_plan.
+static int conv_c1_stencil_oct(bool has_pre, bool has_res, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd,
+                               int kh, int kw, int stride, int pad) {
+  if (C_in != 1 || kd != 3 || kh != 3 || kw != 3 || pad != 1 || (stride != 1 && stride != 2) || has_pre || has_res) return 0;
+  if (stride == 1 && (Do != Di || Ho != Hi || Wo != Wi)) return 0;
+  if (stride == 2 && (Do != (Di + 1) / 2 || Ho != (Hi + 1) / 2 || Wo != (Wi + 1) / 2)) return 0;
+  return C_out >= 32 ? 32 : (C_out >= 8 ? 8 : (C_out > 1 ? 4 : 1));
+}
+
+// -> true when the launch was made (conv_c1_stencil_oct)
 bool conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const float* ab, int act_in, const EpiParams& e, int N,
                          int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
                          int dtype, hipStream_t s) {
-  if (C_in != 1 || kd != 3 || kh != 3 || kw != 3 || pad != 1 || (stride != 1 && stride != 2) || ab || act_in != PYTC_ACT_NONE ||
-      e.res_mode != PYTC_RES_NONE)
-    return false;
-  if (stride == 1 && (Do != Di || Ho != Hi || Wo != Wi)) return false;
-  if (stride == 2 && (Do != (Di + 1) / 2 || Ho != (Hi + 1) / 2 || Wo != (Wi + 1) / 2)) return false;
+  const int oct = conv_c1_stencil_oct(ab != nullptr || act_in != PYTC_ACT_NONE, e.res_mode != PYTC_RES_NONE, Do, Ho, Wo, Di, Hi, Wi, C_in,
+                                      C_out, kd, kh, kw, stride, pad);
+  if (!oct) return false;
   const long total = (long)N * Do * Ho * Wo;
-  const int oct = C_out >= 32 ? 32 : (C_out >= 8 ? 8 : (C_out > 1 ? 4 : 1));
   dim3 grid((unsigned)((total + 255) / 256), (unsigned)((C_out + oct - 1) / oct));
 #define PYTC_C1(TT, OCTV) hipLaunchKernelGGL((conv3d_c1_stencil_kernel<TT, OCTV>), grid, dim3(256), 0, s, (const TT*)x, (const TT*)wp, bias, \
                                              (TT*)e.y, N, Do, Ho, Wo, Di, Hi, Wi, C_out, stride)
@@ -762,13 +769,31 @@ static void launch_conv_phases_mt(const ConvParams& p, const ConvTile& t, const 
   hipLaunchKernelGGL((conv3d_tile_kernel<MT>), grid, dim3(256), lds_bytes, s, p, t, ps);
 }
 
-static void launch_conv_tile(const ConvParams& p, ConvTile t, size_t lds_bytes, hipStream_t s) {
-  t.tiles_z = (p.D + CT_TZ - 1) / CT_TZ; t.tiles_y = (p.H + CT_TY - 1) / CT_TY; t.tiles_x = (p.W + CT_TX - 1) / CT_TX;
-  int MT = p.MTt >= 4 ? 4 : (p.MTt >= 2 ? 2 : 1);
+// 4 x 8 x 16 blocks of a launch over N x D x H x W voxels
+static long conv_tile_spatial(int N, int D, int H, int W) {
+  return (long)N * ((D + CT_TZ - 1) / CT_TZ) * ((H + CT_TY - 1) / CT_TY) * ((W + CT_TX - 1) / CT_TX);
+}
+
+// output-channel tiles per workgroup of the LDS-tiled launch (the one rule of launch_conv_tile and pytc_conv3d_launch_plan)
+static int conv_tile_mt(int MTt, long spatial) {
+  int MT = MTt >= 4 ? 4 : (MTt >= 2 ? 2 : 1);
   // deep levels (2 x 18 x 20 x 20 voxels = 60 spatial tiles): 64 output channels per workgroup leave 120 workgroups for 256 CUs;
   // fewer output tiles per workgroup (every workgroup stages the same input tile: L2 hits) until one per CU exists (more costs level 1 its 64-channel reuse: 40 -> 55 us)
-  const long spatial = (long)p.N * t.tiles_z * t.tiles_y * t.tiles_x;
-  while (MT > 1 && spatial * ((p.MTt + MT - 1) / MT) < 256) MT >>= 1;
+  while (MT > 1 && spatial * ((MTt + MT - 1) / MT) < 256) MT >>= 1;
+  return MT;
+}
+
+// ... and of the eight-phase launch (pytc_convT3d_phase_fwd): as conv_tile_mt, enough workgroups for the chip
+static int conv_phase_mt(int MTt, long spatial) {
+  int MT = MTt >= 4 ? 4 : (MTt >= 2 ? 2 : 1);
+  while (MT > 1 && spatial * 8 * ((MTt + MT - 1) / MT) < 512) MT >>= 1;
+  return MT;
+}
+
+static void launch_conv_tile(const ConvParams& p, ConvTile t, size_t lds_bytes, hipStream_t s) {
+  t.tiles_z = (p.D + CT_TZ - 1) / CT_TZ; t.tiles_y = (p.H + CT_TY - 1) / CT_TY; t.tiles_x = (p.W + CT_TX - 1) / CT_TX;
+  const long spatial = conv_tile_spatial(p.N, p.D, p.H, p.W);
+  const int MT = conv_tile_mt(p.MTt, spatial);
   dim3 grid((unsigned)spatial, (unsigned)((p.MTt + MT - 1) / MT));
   switch (MT) {
     case 1: launch_conv_tile_mt<1>(p, t, lds_bytes, grid, s); break;
@@ -777,17 +802,26 @@ static void launch_conv_tile(const ConvParams& p, ConvTile t, size_t lds_bytes, 
   }
 }
 
+// the gather forms (launch_conv): the thin-input kernel's LDS weight image in bytes, 0 when the MFMA gather kernel serves the conv; the
+// gather kernel's output-channel tiles per workgroup and voxels per workgroup
+static size_t conv_thin_lds(int C_in, int kd, int kh, int kw) {
+  const size_t thin_lds = (size_t)kd * kh * kw * C_in * 16 * sizeof(float);
+  return (C_in <= 4 && thin_lds <= 48 * 1024) ? thin_lds : 0;
+}
+static int conv_gather_mt(int MTt) { return MTt >= 4 ? 4 : (MTt >= 2 ? 2 : 1); }
+constexpr int CG_NT = 4;
+
 template <typename TI, typename TW, typename TO>
 static void launch_conv(const ConvParams& p, hipStream_t s) {
-  constexpr int NT = 4;
+  constexpr int NT = CG_NT;
   const long rps = (long)p.D * p.H * p.W;
-  const size_t thin_lds = (size_t)p.kd * p.kh * p.kw * p.C_in * 16 * sizeof(float);
-  if (p.C_in <= 4 && thin_lds <= 48 * 1024) {
+  const size_t thin_lds = conv_thin_lds(p.C_in, p.kd, p.kh, p.kw);
+  if (thin_lds) {
     dim3 grid((unsigned)((rps + 255) / 256), (unsigned)p.MTt, (unsigned)p.N);
     hipLaunchKernelGGL((conv3d_thin_in_kernel<TI, TW, TO>), grid, dim3(256), thin_lds, s, p);
     return;
   }
-  const int MT = p.MTt >= 4 ? 4 : (p.MTt >= 2 ? 2 : 1);
+  const int MT = conv_gather_mt(p.MTt);
   dim3 grid((unsigned)((rps + 4L * NT * 16 - 1) / (4L * NT * 16)), (unsigned)((p.MTt + MT - 1) / MT), (unsigned)p.N);
   dim3 block(256);
   switch (MT) {
@@ -877,6 +911,15 @@ extern "C" int pytc_conv3d_pack_multi(const int64_t* table_dev, int n_items, int
   return PYTC_OK;
 }
 
+// which kernel pytc_conv3d_fwd launches (the one rule of the launch and of pytc_conv3d_launch_plan); TILE: t / lds_bytes are its plan
+enum { CONV_FORM_STENCIL = 0, CONV_FORM_TILE = 1, CONV_FORM_GATHER = 2, CONV_FORM_THIN = 3 };
+static int conv_fwd_form(int dtype, bool has_pre, bool has_res, int D, int H, int W, int C_in, int C_out, int kd, int kh, int kw,
+                         ConvTile& t, size_t& lds_bytes) {
+  if (conv_c1_stencil_oct(has_pre, has_res, D, H, W, D, H, W, C_in, C_out, kd, kh, kw, 1, 1)) return CONV_FORM_STENCIL;
+  if (conv_tile_plan(dtype, C_in, kd, kh, kw, t, lds_bytes)) return CONV_FORM_TILE;
+  return conv_thin_lds(C_in, kd, kh, kw) ? CONV_FORM_THIN : CONV_FORM_GATHER;
+}
+
 extern "C" int pytc_conv3d_fwd(const pytc_conv3d_args* a, void* stream) {
   PYTC_REQUIRE(a && a->x && a->w_packed && a->y, "conv3d: null pointer");
   PYTC_REQUIRE(a->N >= 1 && a->D >= 1 && a->H >= 1 && a->W >= 1 && a->C_in >= 1 && a->C_out >= 1, "conv3d: bad shape");
@@ -897,11 +940,17 @@ extern "C" int pytc_conv3d_fwd(const pytc_conv3d_args* a, void* stream) {
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   hipStream_t s = (hipStream_t)stream;
   ConvTile t; size_t lds_bytes;
-  if (conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, a->D, a->H, a->W, a->C_in, a->C_out,
-                          a->kd, a->kh, a->kw, 1, 1, a->dtype, s)) {}
-  else if (conv_tile_plan(a->dtype, a->C_in, a->kd, a->kh, a->kw, t, lds_bytes)) launch_conv_tile(p, t, lds_bytes, s);
-  else if (a->dtype == PYTC_F32) launch_conv<float, float, float>(p, s);
-  else launch_conv<bf16_t, bf16_t, bf16_t>(p, s);
+  switch (conv_fwd_form(a->dtype, a->ab != nullptr || a->act_in != PYTC_ACT_NONE, a->res_mode != PYTC_RES_NONE, a->D, a->H, a->W, a->C_in,
+                        a->C_out, a->kd, a->kh, a->kw, t, lds_bytes)) {
+    case CONV_FORM_STENCIL:
+      conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, a->D, a->H, a->W, a->C_in, a->C_out,
+                          a->kd, a->kh, a->kw, 1, 1, a->dtype, s);
+      break;
+    case CONV_FORM_TILE: launch_conv_tile(p, t, lds_bytes, s); break;
+    default:                                                 // (launch_conv picks the thin-input or the MFMA gather kernel)
+      if (a->dtype == PYTC_F32) launch_conv<float, float, float>(p, s);
+      else launch_conv<bf16_t, bf16_t, bf16_t>(p, s);
+  }
   PYTC_LAUNCH_CHECK("conv3d");
   return PYTC_OK;
 }
@@ -967,9 +1016,8 @@ extern "C" int pytc_convT3d_phase_fwd(const pytc_conv3d_args* a, const int32_t* 
     if (lds[ph] > lds_max) lds_max = lds[ph];
   ConvTile tt = t[7];
   tt.tiles_z = (p.D + CT_TZ - 1) / CT_TZ; tt.tiles_y = (p.H + CT_TY - 1) / CT_TY; tt.tiles_x = (p.W + CT_TX - 1) / CT_TX;
-  int MT = p.MTt >= 4 ? 4 : (p.MTt >= 2 ? 2 : 1);
-  const long spatial = (long)p.N * tt.tiles_z * tt.tiles_y * tt.tiles_x;
-  while (MT > 1 && spatial * 8 * ((p.MTt + MT - 1) / MT) < 512) MT >>= 1;       // (as launch_conv_tile: enough workgroups for the chip)
+  const long spatial = conv_tile_spatial(p.N, p.D, p.H, p.W);
+  const int MT = conv_phase_mt(p.MTt, spatial);
   dim3 grid((unsigned)spatial, (unsigned)((p.MTt + MT - 1) / MT), 8);
   switch (MT) {
     case 1: launch_conv_phases_mt<1>(p, tt, ps, lds_max, grid, s); break;
@@ -980,3 +1028,43 @@ extern "C" int pytc_convT3d_phase_fwd(const pytc_conv3d_args* a, const int32_t* 
   return PYTC_OK;
 }
 
+/* Which kernel, and in which launch form, pytc_conv3d_fwd (phase = 0) or pytc_convT3d_phase_fwd (phase = 1) runs for these arguments: built
+   from the functions the launches themselves call (conv_fwd_form, conv_tile_mt, conv_phase_mt, ...), pure host code.  D / H / W: the grid
+   the kernel walks (phase = 1: the INPUT grid of the transposed conv).  out[0] = form (0 one-input-channel stencil, 1 LDS tile, 2 MFMA
+   gather conv3d_kernel, 3 conv3d_thin_in_kernel), out[1] = output-channel tiles per workgroup MT (form 0: channels per thread OCT),
+   out[2..4] = KC, chunks, groups per chunk G of the tile plan (phase = 1: of phase 7; 0 for the other forms), out[5] = workgroups. */
+extern "C" int pytc_conv3d_launch_plan(int N, int D, int H, int W, int C_in, int C_out, int kd, int kh, int kw, int dtype, int has_pre,
+                                       int has_res, int phase, int64_t* out) {
+  PYTC_REQUIRE(out && N >= 1 && D >= 1 && H >= 1 && W >= 1 && C_in >= 1 && C_out >= 1 && kd >= 1 && kh >= 1 && kw >= 1 &&
+               (dtype == PYTC_F32 || dtype == PYTC_BF16), "conv3d_launch_plan: bad arguments");
+  const int MTt = (C_out + 15) / 16;
+  const long spatial = conv_tile_spatial(N, D, H, W);
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (phase) {
+    PYTC_REQUIRE(kd == 3 && kh == 3 && kw == 3, "conv3d_launch_plan: the phase form is kernel 3");
+    ConvTile t[8]; size_t lds[8];
+    if (dtype != PYTC_BF16 || !convT_phase_plan(dtype, C_in, t, lds)) return PYTC_ERR_UNSUPPORTED;
+    const int MT = conv_phase_mt(MTt, spatial);
+    out[0] = CONV_FORM_TILE; out[1] = MT; out[2] = t[7].KC; out[3] = t[7].nchunks; out[4] = t[7].G;
+    out[5] = spatial * ((MTt + MT - 1) / MT) * 8;
+    return PYTC_OK;
+  }
+  PYTC_REQUIRE((kd & 1) && (kh & 1) && (kw & 1), "conv3d_launch_plan: kernel sizes must be odd ('same' padding)");
+  ConvTile t; size_t lds_bytes;
+  const long rps = (long)D * H * W;
+  const int form = conv_fwd_form(dtype, has_pre != 0, has_res != 0, D, H, W, C_in, C_out, kd, kh, kw, t, lds_bytes);
+  out[0] = form;
+  if (form == CONV_FORM_STENCIL) {
+    const int oct = conv_c1_stencil_oct(has_pre != 0, has_res != 0, D, H, W, D, H, W, C_in, C_out, kd, kh, kw, 1, 1);
+    out[1] = oct; out[5] = ((N * rps + 255) / 256) * ((C_out + oct - 1) / oct);
+  } else if (form == CONV_FORM_TILE) {
+    const int MT = conv_tile_mt(MTt, spatial);
+    out[1] = MT; out[2] = t.KC; out[3] = t.nchunks; out[4] = t.G; out[5] = spatial * ((MTt + MT - 1) / MT);
+  } else if (form == CONV_FORM_THIN) {
+    out[1] = 1; out[5] = ((rps + 255) / 256) * MTt * N;
+  } else {
+    const int MT = conv_gather_mt(MTt);
+    out[1] = MT; out[5] = ((rps + 4L * CG_NT * 16 - 1) / (4L * CG_NT * 16)) * ((MTt + MT - 1) / MT) * N;
+  }
+  return PYTC_OK;
+}
