@@ -28,8 +28,10 @@ extern "C" {
  * pytc_copy_zero_front, pytc_dwconv3d_bwd_data_add, pytc_pw_wgrad_groupnorm leaves the per-sample terms in the partials region at sps == 1.
  * 5: pytc_cldice_* (the clDice soft skeleton and its gradient).
  * 6: the key set of pytc_set_tuning is closed: an unknown key returns PYTC_ERR_INVALID (the last error names it).
+ * 7: pytc_conv3d_launch_plan (which kernel and launch form a dense-conv call takes; a host query).
+ * 8: pytc_scnp_* (the neighbour-penalised logits of ScnpLoss, its BCE sums and its gradient).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 7
+#define PYTC_ABI_VERSION 8
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -951,6 +953,27 @@ int pytc_cldice_chain_bwd(const float* p0, const float* P, const float* target, 
 int pytc_cldice_sweep_bwd(const float* p0, const float* P, const float* gdiff, const uint8_t* arg, const float* a_next, float* a_out,
                           const float* skel_t, const float* weight, const float* coef, int nvol, int D, int H, int W, int n_iters,
                           int level, int is2d, void* stream);
+
+/* Same-Class Neighbor Penalization (models/losses/losses.py:354-453, ScnpLoss) on N C fp32 volumes of D x H x W voxels (NCDHW);
+ * is2d 1 for (N, C, H, W) inputs, passed with D = 1 (the window spans H and W only).  ns = neighborhood_size in {1, 3, 5, 7}
+ * (another size returns PYTC_ERR_UNSUPPORTED), r = ns / 2.  The weight w is nullable and has wC = C or 1 channels (1: broadcast
+ * inside the kernels; wC is ignored when w is null).
+ * pytc_scnp_forward: per voxel z~ = the min (centre t > 0.5) or max (otherwise) of the same-class logits of its in-bounds ns^3
+ *   (2-D: ns^2) window, +-9999 standing for the voxels of the other class; bit-identical to the reference's for finite logits.
+ *   arg (required) = the window code ((dz + r) ns + (dy + r)) ns + (dx + r) of the first voxel in (z, y, x) scan order that supplied
+ *   it: uint8 per voxel for ns <= 5, uint16 for ns = 7.  zt (nullable) = z~.  With partial and sums non-null (both or neither):
+ *   sums[5 vol + 0] = sum w [(1 - t) z~ + softplus(-z~)], [+ 1] = sum w t softplus(-z~) (fp32; w = 1 when null; with valid_only
+ *   voxels of w <= 0 add nothing), [+ 2 .. + 4] = the counts of w > 0, of valid t > 0 and of valid t <= 0 as int32 in the same
+ *   4-byte slots; partial = 5 N C pytc_scnp_tiles(D H W) floats, reduced in a fixed order.  BCE with pos_weight pw on z~ is
+ *   sums[0] + (pw - 1) sums[1].
+ * pytc_scnp_backward: dx = the gradient of sum_u coef[vol] bce_pw(z~_u, t_u) w_u in the logits, pw = pos_weight[vol] (both N C
+ *   device floats): every voxel gathers, in a fixed order and without atomics, from the window voxels of its own class whose arg
+ *   names it.  arg is the forward's, valid_only as there. */
+int pytc_scnp_tiles(int64_t voxels);
+int pytc_scnp_forward(const float* x, const float* t, const float* w, void* arg, float* zt, float* partial, float* sums, int N, int C,
+                      int wC, int D, int H, int W, int ns, int is2d, int valid_only, void* stream);
+int pytc_scnp_backward(const float* x, const float* t, const float* w, const void* arg, const float* coef, const float* pos_weight,
+                       float* dx, int N, int C, int wC, int D, int H, int W, int ns, int is2d, int valid_only, void* stream);
 
 #ifdef __cplusplus
 }

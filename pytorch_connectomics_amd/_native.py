@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 7          # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 8          # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -306,6 +306,9 @@ _SIGS = {
     "pytc_cldice_skeleton": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
     "pytc_cldice_chain_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 6 + [C.c_void_p]),
     "pytc_cldice_sweep_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 7 + [C.c_void_p]),
+    "pytc_scnp_tiles": (C.c_int, [C.c_int64]),
+    "pytc_scnp_forward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p]),
+    "pytc_scnp_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p]),
 }
 
 _lib = None

@@ -2316,3 +2316,80 @@ def cldice_backward(prob: torch.Tensor, P: torch.Tensor, num_iters: int, target:
              _p(a_next) if j <= n else None, _p(a_out), _p(skel_t), _p(weight), _p(coef), nvol, D, H, W, n, j, is2d, _stream())
         a_next, a_out = a_out, a_next
     return a_next
+
+
+# ---- ScnpLoss: neighbour-penalised logits, BCE sums and gradient (csrc/scnp_kernels.hip) ------------------------------------------
+SCNP_SIZES = (1, 3, 5, 7)
+
+
+def _scnp_geo(x: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor], ns: int):
+    """(N, C, wC, D, H, W, is2d) of contiguous fp32 logits / target of one shape and a weight of C channels or one."""
+    ns = int(ns)
+    if ns < 1 or ns % 2 == 0:
+        raise ValueError(f"neighborhood_size must be a positive odd int, got {ns}.")
+    if ns not in SCNP_SIZES:
+        raise NotImplementedError(f"neighborhood_size={ns}: the HIP kernels are built for neighborhood_size in {SCNP_SIZES}; "
+                                  "larger windows run on CPU tensors only")
+    _dev(x, "logits")
+    _dev(t, "target")
+    if x.dtype != torch.float32 or t.dtype != torch.float32 or t.shape != x.shape:
+        raise ValueError(f"logits and target must be float32 of one shape, got {x.dtype} {tuple(x.shape)} and {t.dtype} {tuple(t.shape)}")
+    if x.dim() == 5:
+        N, C_, D, H, W = (int(v) for v in x.shape)
+        is2d = 0
+    elif x.dim() == 4:
+        N, C_, H, W = (int(v) for v in x.shape)
+        D, is2d = 1, 1
+    else:
+        raise ValueError(f"ScnpLoss expects 4D [B,C,H,W] or 5D [B,C,Z,Y,X] logits, got {x.dim()}D.")
+    wC = C_
+    if w is not None:
+        _dev(w, "weight")
+        wC = int(w.shape[1]) if w.dim() == x.dim() else -1
+        if w.dtype != torch.float32 or wC not in (1, C_) or w.shape[0] != x.shape[0] or w.shape[2:] != x.shape[2:]:
+            raise ValueError(f"weight must be float32 of shape {tuple(x.shape)} or with one channel, got {w.dtype} {tuple(w.shape)}")
+    return N, C_, wC, D, H, W, is2d
+
+
+def scnp_forward(x: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor], ns: int, *, valid_only: bool = True,
+                 want_sums: bool = True, want_logits: bool = False):
+    """-> (arg, sums, counts, z~): the supplier code map (uint8, int16 bits at ns = 7), the fp32 sums (N, C, 2) =
+    (sum w [(1 - t) z~ + softplus(-z~)], sum w t softplus(-z~)), the int32 counts (N, C, 3) = (w > 0, valid t > 0, valid t <= 0) and,
+    on request, z~ itself.  No host synchronisation."""
+    N, C_, wC, D, H, W, is2d = _scnp_geo(x, t, w, ns)
+    lib = nat.lib()
+    arg = torch.empty(x.shape, dtype=torch.uint8 if int(ns) <= 5 else torch.int16, device=x.device)
+    zt = torch.empty_like(x) if want_logits else None
+    sums = part = None
+    if want_sums:
+        sums = torch.empty((N, C_, 5), dtype=torch.float32, device=x.device)
+        part = torch.empty((N * C_ * lib.pytc_scnp_tiles(D * H * W) * 5,), dtype=torch.float32, device=x.device)
+    _run(f"scnp_forward[ns={int(ns)}]", _nbytes(x, t, w, arg, zt), lib.pytc_scnp_forward, _p(x), _p(t), _p(w), _p(arg), _p(zt), _p(part),
+         _p(sums), N, C_, wC, D, H, W, int(ns), is2d, int(bool(valid_only)), _stream(), symbol="scnp_forward")
+    if sums is None:
+        return arg, None, None, zt
+    return arg, sums[..., :2], sums.view(torch.int32)[..., 2:], zt
+
+
+def scnp_backward(x: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor], arg: torch.Tensor, coef: torch.Tensor,
+                  pos_weight: torch.Tensor, ns: int, *, valid_only: bool = True) -> torch.Tensor:
+    """The gradient in the logits of sum_u coef bce_pw(z~_u, t_u) w_u; coef and pos_weight are (N, C) device tensors, arg the
+    forward's code map."""
+    N, C_, wC, D, H, W, is2d = _scnp_geo(x, t, w, ns)
+    _dev(arg, "arg")
+    if arg.shape != x.shape or arg.dtype != (torch.uint8 if int(ns) <= 5 else torch.int16):
+        raise ValueError(f"arg must be the code map scnp_forward wrote for neighborhood_size={int(ns)}, got {arg.dtype} {tuple(arg.shape)}")
+    coef = _dev(coef.to(torch.float32).contiguous(), "coef")
+    pos_weight = _dev(pos_weight.to(torch.float32).contiguous(), "pos_weight")
+    if coef.numel() != N * C_ or pos_weight.numel() != N * C_:
+        raise ValueError(f"coef and pos_weight must hold {N} x {C_} values, got {coef.numel()} and {pos_weight.numel()}")
+    dx = torch.empty_like(x)
+    _run(f"scnp_backward[ns={int(ns)}]", _nbytes(x, t, w, arg, dx), nat.lib().pytc_scnp_backward, _p(x), _p(t), _p(w), _p(arg),
+         _p(coef), _p(pos_weight), _p(dx), N, C_, wC, D, H, W, int(ns), is2d, int(bool(valid_only)), _stream(), symbol="scnp_backward")
+    return dx
+
+
+def scnp_logits(x: torch.Tensor, t: torch.Tensor, ns: int) -> torch.Tensor:
+    """The reference's `ScnpLoss._scnp_logits(x, t)` (models/losses/losses.py:414-437) on HIP, bit-identical in fp32 for finite
+    logits: x, t are (N, C, D, H, W) or (N, C, H, W)."""
+    return scnp_forward(x.contiguous(), t.contiguous(), None, ns, want_sums=False, want_logits=True)[3]

@@ -22,6 +22,7 @@ from ..models import build_model
 from ..utils.channel_slices import resolve_channel_indices
 from ..utils.model_outputs import resolve_head_target_slice, unwrap_main_output
 from .cldice_autograd import SoftClDiceLoss, soft_cldice_term
+from .scnp_autograd import ScnpLoss, scnp_term
 
 _NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d,
                nn.InstanceNorm2d, nn.InstanceNorm3d, nn.LayerNorm, nn.LocalResponseNorm)
@@ -134,7 +135,7 @@ def class_balance_weight(target: torch.Tensor, pos_weight=None, valid_mask=None,
 # losses whose spatial argument is a WEIGHT map (reference models/losses/metadata.py:38-48); every other loss sees a mask as
 # "logits at the clamp minimum, target 0" outside it
 _WEIGHT_TAKING = {"SmoothL1Loss", "WeightedBCEWithLogitsLoss", "PerChannelBCEWithLogitsLoss", "WeightedMSELoss", "WeightedMAELoss",
-                  "SoftClDiceLoss"}
+                  "SoftClDiceLoss", "ScnpLoss"}
 _OWN_CLASS_BALANCE = {"WeightedBCEWithLogitsLoss", "PerChannelBCEWithLogitsLoss"}      # pos_weight defaults to 1 there (plan.py:105-112)
 
 
@@ -238,6 +239,9 @@ _LOSSES = {
     # topology loss (losses.py:456-721): soft skeletons on HIP for CUDA tensors (training/cldice_autograd.py)
     "SoftClDiceLoss": lambda p, t, **kw: soft_cldice_term(p, t, kw.get("weight"),
                                                           **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
+    # neighbour-penalised per-channel BCE (losses.py:354-453): pooled logits, sums and gradient on HIP (training/scnp_autograd.py)
+    "ScnpLoss": lambda p, t, **kw: scnp_term(p, t, kw.get("weight"),
+                                             **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
 }
 
 
@@ -413,6 +417,8 @@ class ConnectomicsModule(nn.Module):
                 raise ValueError(f"Unknown loss function {fn!r}; available: {sorted(_LOSSES)}")
             if fn == "SoftClDiceLoss":
                 SoftClDiceLoss(**dict(get("kwargs", None) or {}))      # its argument checks run when the module is built, as there
+            if fn == "ScnpLoss":
+                ScnpLoss(**dict(get("kwargs", None) or {}))
             pos_weight = get("pos_weight")
             if isinstance(pos_weight, str):
                 if pos_weight.strip().lower() != "auto":
