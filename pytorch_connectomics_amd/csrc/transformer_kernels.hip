@@ -295,6 +295,15 @@ __device__ __forceinline__ float win_add(const WinArgs& wa, const int* sm, int i
   return sm[AT_T + i] != sm[3 * AT_T + j] ? b - 100.f : b;
 }
 
+// The scaled score, rounded ONCE and never fused into a later add.  The forward builds its running maximum and the saved lse from this
+// number and the backward recomputes P = expf(score - lse) from it: were the multiply contracted into the subtraction on one side
+// only (scale = 32^-0.5 is not a power of two, so the product rounds), a row whose softmax is exactly one-hot would get
+// P = expf(rounding error of the score) != 1 in the backward.
+__device__ __forceinline__ float scaled_score(float s, float scale) {
+#pragma clang fp contract(off)
+  return s * scale;
+}
+
 template <typename T, int D>
 __device__ __forceinline__ void attn_stage(float* s, const T* qkv, long row_stride, int col, int b, int N, int r0) {
   // s[i][c] (pitch D + 1) = qkv[(b * N + r0 + i) * row_stride + col + c], zero past N
@@ -376,7 +385,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const T* __restrict__ qkv
       float mx = -INFINITY;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        float sc = S[r][s] * scale;
+        float sc = scaled_score(S[r][s], scale);
         if constexpr (WIN) sc += win_add(wa, sM, ti + 16 * r, tj + 16 * s, hd, heads);
         S[r][s] = j0 + tj + 16 * s < N ? sc : -INFINITY;
         mx = fmaxf(mx, S[r][s]);
@@ -450,7 +459,7 @@ __device__ __forceinline__ void attn_p_ds(const float* sQ, const float* sK, cons
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int j = tj + 16 * s;
-      float sc = S[r][s] * scale;
+      float sc = scaled_score(S[r][s], scale);
       if constexpr (WIN) sc += win_add(wa, sM, i, j, hd, heads);
       const float pv = (qok && j0 + j < N) ? expf(sc - slse[i]) : 0.f;
       sP[i * (AT_T + 1) + j] = pv;
