@@ -30,8 +30,9 @@ extern "C" {
  * 6: the key set of pytc_set_tuning is closed: an unknown key returns PYTC_ERR_INVALID (the last error names it).
  * 7: pytc_conv3d_launch_plan (which kernel and launch form a dense-conv call takes; a host query).
  * 8: pytc_scnp_* (the neighbour-penalised logits of ScnpLoss, its BCE sums and its gradient).
+ * 9: pytc_reg_* and pytc_fgcontour_* (the regularisation losses: streaming sums and gradients, the foreground / contour stencil).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 8
+#define PYTC_ABI_VERSION 9
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -974,6 +975,44 @@ int pytc_scnp_forward(const float* x, const float* t, const float* w, void* arg,
                       int wC, int D, int H, int W, int ns, int is2d, int valid_only, void* stream);
 int pytc_scnp_backward(const float* x, const float* t, const float* w, const void* arg, const float* coef, const float* pos_weight,
                        float* dx, int N, int C, int wC, int D, int H, int W, int ns, int is2d, int valid_only, void* stream);
+
+/* The regularisation losses of models/losses/regularization.py on fp32 contiguous tensors of N C volumes of V voxels.  Every sum
+ * comes from fixed-order partials (no atomics: bit-reproducible); nothing synchronises with the host.
+ * Streaming pair.  kind = PYTC_REG_BINARY (operand a), _FG_DIST, _CT_DIST (operands a and b, one shape) or _NONOVERLAP (a alone: an
+ * (N, C, V) tensor, C >= 2, whose channels 0, 1 and -- with flag set and C >= 3 -- 2 are read in place; b and mask must be null).
+ * Per voxel, with s = sigmoid, t = tanh b:
+ *   BINARY      1 / max(|s(a) - 0.5|, param); flag 0 reads a as the probability.  param = min_threshold.  No gradient where the
+ *               clamp is active.
+ *   FG_DIST     softplus(-a) max(t, 0) + softplus(a) max(-t, 0)
+ *   CT_DIST     (s(a) |t|)^2
+ *   NONOVERLAP  s(a0) s(a1) [s(a2)]; a2 is a constant of the gradient.
+ * mask is nullable and has wC = C or 1 channels (1: broadcast inside the kernels; wC is ignored when mask is null).
+ * pytc_reg_pointwise_forward: sum[0] = the sum of mask x loss over the whole tensor; partial = pytc_reg_tiles(V) floats per volume
+ *   (N C volumes; N for NONOVERLAP), reduced in a fixed order by a second launch.
+ * pytc_reg_pointwise_backward: da (and db for the two-operand kinds) = coef[0] x mask x d loss / d operand, recomputed from the
+ *   operands; coef is one device float.  For NONOVERLAP da is the whole (N, C, V) gradient: zero in every channel but 0 and 1.
+ * Stencil pair (ForegroundContourConsistency), fg / contour / mask of (N, 1, D, H, W): per z-plane p = s(fg), ex = p[x - 1] - p[x + 1],
+ * ey = p[y - 1] - p[y + 1] (zeros outside the plane), e = clamp(sqrt(ex^2 + ey^2 + eps), eps, 1 - eps), E = the 3 x 3 in-plane maximum
+ * of e over in-bounds voxels, loss = (E - s(contour))^2 mask.  0 < eps < 0.5.
+ * pytc_fgcontour_forward: sum[0] = the sum of the loss; code (uint8 per voxel) = 3 (dy + 1) + (dx + 1) of the first maximum of the
+ *   window in (y, x) scan order (torch's tie rule); partial = N pytc_fgcontour_tiles(D, H, W) floats.
+ * pytc_fgcontour_backward: dcontour pointwise, dfg as a gather in a fixed order (every voxel from the at most four edge voxels its
+ *   probability enters, every edge voxel from the at most nine pooled outputs whose code names it); the clamp passes gradient where
+ *   eps <= sqrt(...) <= 1 - eps.  code is the forward's; everything else is recomputed. */
+#define PYTC_REG_BINARY 0
+#define PYTC_REG_FG_DIST 1
+#define PYTC_REG_CT_DIST 2
+#define PYTC_REG_NONOVERLAP 3
+int pytc_reg_tiles(int64_t voxels);
+int pytc_reg_pointwise_forward(int kind, const float* a, const float* b, const float* mask, float* partial, float* sum, int N, int C,
+                               int wC, int64_t V, float param, int flag, void* stream);
+int pytc_reg_pointwise_backward(int kind, const float* a, const float* b, const float* mask, const float* coef, float* da, float* db,
+                                int N, int C, int wC, int64_t V, float param, int flag, void* stream);
+int pytc_fgcontour_tiles(int D, int H, int W);
+int pytc_fgcontour_forward(const float* fg, const float* contour, const float* mask, uint8_t* code, float* partial, float* sum, int N,
+                           int D, int H, int W, double eps, void* stream);
+int pytc_fgcontour_backward(const float* fg, const float* contour, const float* mask, const uint8_t* code, const float* coef,
+                            float* dfg, float* dcontour, int N, int D, int H, int W, double eps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2393,3 +2393,118 @@ def scnp_logits(x: torch.Tensor, t: torch.Tensor, ns: int) -> torch.Tensor:
     """The reference's `ScnpLoss._scnp_logits(x, t)` (models/losses/losses.py:414-437) on HIP, bit-identical in fp32 for finite
     logits: x, t are (N, C, D, H, W) or (N, C, H, W)."""
     return scnp_forward(x.contiguous(), t.contiguous(), None, ns, want_sums=False, want_logits=True)[3]
+
+
+# ---- regularisation losses: streaming sums / gradients and the foreground-contour stencil (csrc/regularization_kernels.hip) ---------
+REG_KINDS = {"binary": 0, "fg_dist": 1, "ct_dist": 2, "nonoverlap": 3}
+
+
+def _reg_geo(kind: str, a: torch.Tensor, b: Optional[torch.Tensor], mask: Optional[torch.Tensor]):
+    """(kind code, N, C, wC, V) of contiguous fp32 operands (N, C, ...) of one shape and a mask of C channels or one."""
+    if kind not in REG_KINDS:
+        raise ValueError(f"unknown regularisation kind {kind!r}; available: {sorted(REG_KINDS)}")
+    _dev(a, "pred")
+    if a.dtype != torch.float32 or a.dim() < 2:
+        raise ValueError(f"pred must be float32 of shape (N, C, ...), got {a.dtype} {tuple(a.shape)}")
+    two = kind in ("fg_dist", "ct_dist")
+    if two != (b is not None):
+        raise ValueError(f"kind {kind!r} takes {'two operands' if two else 'one operand'}")
+    if b is not None:
+        _dev(b, "pred2")
+        if b.dtype != torch.float32 or b.shape != a.shape:
+            raise ValueError(f"pred and pred2 must be float32 of one shape, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    N, C_ = int(a.shape[0]), int(a.shape[1])
+    V = 1
+    for v in a.shape[2:]:
+        V *= int(v)
+    if a.numel() == 0:
+        raise ValueError(f"pred is empty: {tuple(a.shape)}")
+    wC = C_
+    if kind == "nonoverlap":
+        if C_ < 2:
+            raise ValueError(f"Expected at least 2 channels for pre/post predictions, got {C_}")
+        if mask is not None:
+            raise ValueError("NonOverlapRegularization takes no mask")
+    elif mask is not None:
+        _dev(mask, "mask")
+        wC = int(mask.shape[1]) if mask.dim() == a.dim() else -1
+        if mask.dtype != torch.float32 or wC not in (1, C_) or mask.shape[0] != a.shape[0] or mask.shape[2:] != a.shape[2:]:
+            raise ValueError(f"mask must be float32 of shape {tuple(a.shape)} or with one channel, got {mask.dtype} {tuple(mask.shape)}")
+    return REG_KINDS[kind], N, C_, wC, V
+
+
+def reg_pointwise_forward(kind: str, a: torch.Tensor, b: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, *,
+                          param: float = 0.0, flag: bool = True) -> torch.Tensor:
+    """-> the fp32 sum (shape (1,)) of mask x loss over the whole tensor for kind 'binary' (param = min_threshold, flag = apply_sigmoid),
+    'fg_dist', 'ct_dist' or 'nonoverlap' (flag = cleft_masked).  No host synchronisation."""
+    k, N, C_, wC, V = _reg_geo(kind, a, b, mask)
+    lib = nat.lib()
+    out = torch.empty((1,), dtype=torch.float32, device=a.device)
+    part = torch.empty(((N if kind == "nonoverlap" else N * C_) * lib.pytc_reg_tiles(V),), dtype=torch.float32, device=a.device)
+    _run(f"reg_pointwise_forward[{kind}]", _nbytes(a, b, mask), lib.pytc_reg_pointwise_forward, k, _p(a), _p(b), _p(mask), _p(part),
+         _p(out), N, C_, wC, V, float(param), int(bool(flag)), _stream(), symbol="reg_forward")
+    return out
+
+
+def reg_pointwise_backward(kind: str, coef: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None,
+                           mask: Optional[torch.Tensor] = None, *, param: float = 0.0, flag: bool = True):
+    """-> (da, db): coef x mask x the gradient of the loss in each operand (db None for the one-operand kinds); coef is one device
+    float.  For 'nonoverlap' da is the gradient of the whole (N, C, ...) tensor, zero outside channels 0 and 1."""
+    k, N, C_, wC, V = _reg_geo(kind, a, b, mask)
+    coef = _dev(coef.to(torch.float32).reshape(-1).contiguous(), "coef")
+    if coef.numel() != 1:
+        raise ValueError(f"coef must hold one value, got {coef.numel()}")
+    da = torch.empty_like(a)
+    db = torch.empty_like(b) if b is not None else None
+    _run(f"reg_pointwise_backward[{kind}]", _nbytes(a, b, mask, da, db), nat.lib().pytc_reg_pointwise_backward, k, _p(a), _p(b), _p(mask),
+         _p(coef), _p(da), _p(db), N, C_, wC, V, float(param), int(bool(flag)), _stream(), symbol="reg_backward")
+    return da, db
+
+
+def _fgcontour_geo(fg: torch.Tensor, contour: torch.Tensor, mask: Optional[torch.Tensor], eps: float):
+    _dev(fg, "foreground_logits")
+    _dev(contour, "contour_logits")
+    if fg.dim() != 5 or fg.shape[1] != 1 or contour.shape != fg.shape:
+        raise ValueError("ForegroundContourConsistency takes 5-D single-channel inputs (N, 1, D, H, W) of one shape, got "
+                         f"{tuple(fg.shape)} and {tuple(contour.shape)}")
+    if fg.dtype != torch.float32 or contour.dtype != torch.float32:
+        raise ValueError(f"foreground and contour logits must be float32, got {fg.dtype} and {contour.dtype}")
+    if fg.numel() == 0:
+        raise ValueError(f"foreground_logits is empty: {tuple(fg.shape)}")
+    if mask is not None:
+        _dev(mask, "mask")
+        if mask.dtype != torch.float32 or mask.shape != fg.shape:
+            raise ValueError(f"mask must be float32 of shape {tuple(fg.shape)}, got {mask.dtype} {tuple(mask.shape)}")
+    if not 0.0 < float(eps) < 0.5:
+        raise ValueError(f"eps must lie in (0, 0.5) for the HIP kernels, got {eps}")
+    N, _, D, H, W = (int(v) for v in fg.shape)
+    return N, D, H, W
+
+
+def fgcontour_forward(fg: torch.Tensor, contour: torch.Tensor, mask: Optional[torch.Tensor] = None, *, eps: float = 1e-7):
+    """-> (sum (1,), code): the sum of (E - sigmoid(contour))^2 mask, E the 3 x 3 in-plane maximum of the clamped Sobel magnitude of
+    sigmoid(fg), and the uint8 map of which window position (0 .. 8, first maximum in scan order) supplied E."""
+    N, D, H, W = _fgcontour_geo(fg, contour, mask, eps)
+    lib = nat.lib()
+    out = torch.empty((1,), dtype=torch.float32, device=fg.device)
+    code = torch.empty(fg.shape, dtype=torch.uint8, device=fg.device)
+    part = torch.empty((N * lib.pytc_fgcontour_tiles(D, H, W),), dtype=torch.float32, device=fg.device)
+    _run("fgcontour_forward", _nbytes(fg, contour, mask, code), lib.pytc_fgcontour_forward, _p(fg), _p(contour), _p(mask), _p(code),
+         _p(part), _p(out), N, D, H, W, float(eps), _stream())
+    return out, code
+
+
+def fgcontour_backward(coef: torch.Tensor, fg: torch.Tensor, contour: torch.Tensor, mask: Optional[torch.Tensor], code: torch.Tensor, *,
+                       eps: float = 1e-7):
+    """-> (dfg, dcontour) of coef x the forward's sum; code is the forward's map, coef one device float."""
+    N, D, H, W = _fgcontour_geo(fg, contour, mask, eps)
+    _dev(code, "code")
+    if code.shape != fg.shape or code.dtype != torch.uint8:
+        raise ValueError(f"code must be the uint8 map fgcontour_forward wrote, got {code.dtype} {tuple(code.shape)}")
+    coef = _dev(coef.to(torch.float32).reshape(-1).contiguous(), "coef")
+    if coef.numel() != 1:
+        raise ValueError(f"coef must hold one value, got {coef.numel()}")
+    dfg, dct = torch.empty_like(fg), torch.empty_like(contour)
+    _run("fgcontour_backward", _nbytes(fg, contour, mask, code, dfg, dct), nat.lib().pytc_fgcontour_backward, _p(fg), _p(contour),
+         _p(mask), _p(code), _p(coef), _p(dfg), _p(dct), N, D, H, W, float(eps), _stream())
+    return dfg, dct

@@ -22,6 +22,7 @@ from ..models import build_model
 from ..utils.channel_slices import resolve_channel_indices
 from ..utils.model_outputs import resolve_head_target_slice, unwrap_main_output
 from .cldice_autograd import SoftClDiceLoss, soft_cldice_term
+from .regularization_autograd import REGULARIZATION_LOSSES
 from .scnp_autograd import ScnpLoss, scnp_term
 
 _NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d,
@@ -243,6 +244,11 @@ _LOSSES = {
     "ScnpLoss": lambda p, t, **kw: scnp_term(p, t, kw.get("weight"),
                                              **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
 }
+# the regularisers (models/losses/regularization.py; value and gradients on HIP, training/regularization_autograd.py) take no target:
+# a `pred_only` loss is called on one prediction slice, a `pred_pred` loss on two, and those with a `mask` argument get the term's
+# combined mask (models/losses/metadata.py:53-76).  A term holds its loss instance, built once with the module.
+_LOSSES.update({name: cls for name, (cls, _kind, _arg) in REGULARIZATION_LOSSES.items()})
+_CALL_KINDS = {name: (kind, arg) for name, (_cls, kind, arg) in REGULARIZATION_LOSSES.items()}     # every other loss: pred_target
 
 
 def match_target_to_output(target: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
@@ -419,6 +425,13 @@ class ConnectomicsModule(nn.Module):
                 SoftClDiceLoss(**dict(get("kwargs", None) or {}))      # its argument checks run when the module is built, as there
             if fn == "ScnpLoss":
                 ScnpLoss(**dict(get("kwargs", None) or {}))
+            # how the loss is called (training/losses/plan.py:158-237): the kind is the loss's own; a term may restate it
+            where = f"losses[{len(self.loss_terms)}]"
+            own_kind, spatial_arg = _CALL_KINDS.get(fn, ("pred_target", None))
+            call_kind = str(get("call_kind", get("call", own_kind)))
+            if call_kind != own_kind:
+                raise ValueError(f"Unsupported call_kind {call_kind!r} in {where}")
+            loss_module = _LOSSES[fn](**dict(get("kwargs", None) or {})) if fn in _CALL_KINDS else None
             pos_weight = get("pos_weight")
             if isinstance(pos_weight, str):
                 if pos_weight.strip().lower() != "auto":
@@ -426,30 +439,38 @@ class ConnectomicsModule(nn.Module):
                 pos_weight = "auto"
             elif pos_weight is not None and float(pos_weight) <= 0:
                 raise ValueError(f"losses[{len(self.loss_terms)}] pos_weight must be > 0, got {float(pos_weight)}")
-            if pos_weight is not None and fn not in _WEIGHT_TAKING:
-                raise ValueError(f"losses[{len(self.loss_terms)}] pos_weight is only supported for losses with "
-                                 f"spatial_weight_arg='weight' (got {fn})")
             # which head a term reads is settled when the module is built (training/losses/plan.py:183-229): pred_head, else
             # model.primary_head, else the only head; a term that names no target channels takes that head's `target_slice`
             heads = getattr(cfg.model, "heads", None)
             heads = heads if isinstance(heads, Mapping) else {}
-            where, pred_head, primary = f"losses[{len(self.loss_terms)}]", get("pred_head"), getattr(cfg.model, "primary_head", None)
+            pred_head, pred2_head, primary = get("pred_head"), get("pred2_head"), getattr(cfg.model, "primary_head", None)
             if heads:
                 if pred_head is not None and pred_head not in heads:
                     raise ValueError(f"{where} pred_head={pred_head!r} is not one of the configured model.heads {sorted(heads)}")
+                if pred2_head is not None and pred2_head not in heads:
+                    raise ValueError(f"{where} pred2_head={pred2_head!r} is not one of the configured model.heads {sorted(heads)}")
                 if pred_head is None and primary is None and len(heads) > 1:
                     raise ValueError(f"{where} must define pred_head or model.primary_head when model.heads has multiple entries "
                                      f"{sorted(heads)}")
-            elif pred_head is not None:
+            elif pred_head is not None or pred2_head is not None:
                 raise ValueError(f"{where} uses pred_head/pred2_head but model.heads is not configured.")
+            pred_slice, pred2_slice = get("pred_slice", get("pred")), get("pred2_slice", get("pred2"))
+            if call_kind == "pred_only" and pred_slice is None:
+                raise ValueError(f"{where} pred_only terms require pred_slice")
+            if call_kind == "pred_pred" and (pred_slice is None or pred2_slice is None):
+                raise ValueError(f"{where} pred_pred terms require pred_slice and pred2_slice")
+            if pos_weight is not None and fn not in _WEIGHT_TAKING:
+                raise ValueError(f"{where} pos_weight is only supported for losses with "
+                                 f"spatial_weight_arg='weight' (got {fn})")
             target_slice = get("target_slice", get("target"))
-            if target_slice is None:
+            if target_slice is None and call_kind == "pred_target":
                 head = pred_head or primary or (next(iter(heads)) if len(heads) == 1 else None)
                 if head is not None:
                     target_slice = resolve_head_target_slice(cfg, head)
             # the reference's spellings (training/losses/plan.py:126-147): coefficient = weight, pred / target / mask = *_slice
             self.loss_terms.append({"fn": fn, "weight": float(get("coefficient", get("weight", 1.0))), "pred_head": get("pred_head"),
-                                    "pred_slice": get("pred_slice", get("pred")),
+                                    "pred_slice": pred_slice, "call_kind": call_kind, "pred2_slice": pred2_slice,
+                                    "pred2_head": pred2_head, "spatial_arg": spatial_arg, "loss": loss_module,
                                     "target_slice": target_slice, "pos_weight": pos_weight,
                                     "mask_slice": get("mask_slice", get("mask")),
                                     "apply_deep_supervision": bool(get("apply_deep_supervision", True)),
@@ -522,18 +543,33 @@ class ConnectomicsModule(nn.Module):
         plain_bce_masked = mask is not None and any(t["fn"] == "BCEWithLogitsLoss" for _, t in terms)
         return bool(pred.is_cuda and self.fused_loss and not plain_bce_masked and all(self._term_is_fusable(t, pred) for _, t in terms))
 
-    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None):
+    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None):
         """Weighted sum of the loss terms `terms` (list of (index, term); default: all) on one prediction tensor.
         tasks: a dict that receives {term index: static weight x raw value, WITH its graph} (adaptive balancing: the caller
-        combines the tasks); the fused kernel steps aside then -- it returns one scalar for all its terms."""
+        combines the tasks); the fused kernel steps aside then -- it returns one scalar for all its terms.
+        heads: the named-head outputs, for a `pred_pred` term whose second slice comes from another head."""
         terms = list(enumerate(self.loss_terms)) if terms is None else terms
         pred = torch.clamp(pred, min=self.clamp_min, max=self.clamp_max)
-        if tasks is None and self._fusable(pred, mask, terms):
-            res = self._fused_term_loss(pred, target, mask, terms)      # finiteness is checked where fit() reads the value
-            if res is not None:
-                return res
         total, parts = 0.0, {}
+        if tasks is None:
+            # the terms without a target (regularisers) never enter the fused reduction and must not push the supervised terms off
+            # it: those are judged on their own, the rest is added below
+            supervised = [(i, t) for i, t in terms if t.get("call_kind", "pred_target") == "pred_target"]
+            if supervised and self._fusable(pred, mask, supervised):
+                res = self._fused_term_loss(pred, target, mask, supervised)      # finiteness is checked where fit() reads the value
+                if res is not None:
+                    if len(supervised) == len(terms):
+                        return res
+                    total, parts = res
+                    terms = [(i, t) for i, t in terms if t.get("call_kind", "pred_target") != "pred_target"]
         for i, t in terms:
+            if t.get("call_kind", "pred_target") != "pred_target":
+                v = self._regularizer_loss(i, t, pred, target, mask, heads)
+                parts[f"loss_{i}_{t['fn']}"] = v.detach()
+                if tasks is not None:
+                    tasks[i] = t["weight"] * v
+                total = total + t["weight"] * v
+                continue
             p, y = pred, target
             if t["pred_slice"] is not None:
                 p = pred[:, resolve_channel_indices(t["pred_slice"], num_channels=pred.shape[1], context="pred_slice")]
@@ -570,7 +606,33 @@ class ConnectomicsModule(nn.Module):
             total = total + t["weight"] * v
         return total, parts
 
-    def _balanced_scale_loss(self, items, stage: str):
+    def _regularizer_loss(self, i, t, pred, target, mask, heads):
+        """A `pred_only` / `pred_pred` term (training/losses/orchestrator.py:533-718): one or two slices of the clamped predictions
+        -- the second from `pred2_head` when the model has named heads --, no target, and as `mask` the term's `mask_slice` channels
+        of the labels x the batch mask, for the losses that take one."""
+        args = [pred[:, resolve_channel_indices(t["pred_slice"], num_channels=pred.shape[1], context="pred_slice")]]
+        if t["call_kind"] == "pred_pred":
+            src = pred
+            if heads is not None and t.get("pred2_head") is not None:
+                if t["pred2_head"] not in heads:
+                    raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' requested pred2_head='{t['pred2_head']}', but available output "
+                                     f"heads are {sorted(heads)}.")
+                src = torch.clamp(heads[t["pred2_head"]], min=self.clamp_min, max=self.clamp_max)
+            args.append(src[:, resolve_channel_indices(t["pred2_slice"], num_channels=src.shape[1], context="pred2_slice")])
+        combined = None
+        if t.get("mask_slice") is not None:
+            combined = target[:, resolve_channel_indices(t["mask_slice"], num_channels=target.shape[1], context="mask_slice")]
+        if mask is not None:
+            combined = mask if combined is None else combined * mask
+        if t["spatial_arg"] == "mask" and combined is not None:
+            v = t["loss"](*args, mask=combined)
+        else:
+            v = t["loss"](*args)
+        if not torch.isfinite(v):
+            raise FloatingPointError(f"loss term {t['fn']} is not finite")
+        return v
+
+    def _balanced_scale_loss(self, items, stage: str, heads=None):
         """One output scale under adaptive loss balancing (orchestrator.py:110-127, 779-790): `items` = [(pred, target, mask, terms)]
         (one entry per head); every term is a task whose loss is its static weight x raw value, the weighter combines ALL tasks of
         the scale in one call.  Uncertainty weighting on fusable terms keeps the fused HIP loss: the per-task coefficients
@@ -613,7 +675,7 @@ class ConnectomicsModule(nn.Module):
             parts = {}
         tasks: Dict[int, torch.Tensor] = {}
         for pred, target, mask, terms in items:
-            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks)
+            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks, heads=heads)
             parts.update(pr)
         total, wts, logs = w.combine([tasks[i] for i in idx], names, stage)
         for n, wt in zip(names, wts):
@@ -653,10 +715,11 @@ class ConnectomicsModule(nn.Module):
                 by_head.setdefault(self._head_of(i, t, main), []).append((i, t))
             total, parts = 0.0, {}
             if self.loss_weighter is not None:
-                total, parts = self._balanced_scale_loss([(main[head], labels, mask, terms) for head, terms in by_head.items()], stage)
+                total, parts = self._balanced_scale_loss([(main[head], labels, mask, terms) for head, terms in by_head.items()], stage,
+                                                         heads=main)
             else:
                 for head, terms in by_head.items():
-                    v, pr = self._term_loss(main[head], labels, mask, terms)
+                    v, pr = self._term_loss(main[head], labels, mask, terms, heads=main)
                     total = total + v
                     parts.update(pr)
             total = self.ds_weights[0] * total
@@ -665,6 +728,9 @@ class ConnectomicsModule(nn.Module):
         for i, t in enumerate(self.loss_terms):
             if t["pred_head"] is not None:
                 raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' requested pred_head='{t['pred_head']}' but the model "
+                                 "output is a single tensor.")
+            if t.get("pred2_head") is not None:
+                raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' requested pred2_head='{t['pred2_head']}' but the model "
                                  "output is a single tensor.")
         all_terms = list(enumerate(self.loss_terms))
         if self.loss_weighter is not None:
