@@ -31,8 +31,9 @@ extern "C" {
  * 7: pytc_conv3d_launch_plan (which kernel and launch form a dense-conv call takes; a host query).
  * 8: pytc_scnp_* (the neighbour-penalised logits of ScnpLoss, its BCE sums and its gradient).
  * 9: pytc_reg_* and pytc_fgcontour_* (the regularisation losses: streaming sums and gradients, the foreground / contour stencil).
+ * 10: pytc_softmax_loss_* (the channel softmax reduced to eight sums per (sample, class), and its gradient: the softmax losses).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 9
+#define PYTC_ABI_VERSION 10
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1013,6 +1014,32 @@ int pytc_fgcontour_forward(const float* fg, const float* contour, const float* m
                            int D, int H, int W, double eps, void* stream);
 int pytc_fgcontour_backward(const float* fg, const float* contour, const float* mask, const uint8_t* code, const float* coef,
                             float* dfg, float* dcontour, int N, int D, int H, int W, double eps, void* stream);
+
+/* The softmax losses (CrossEntropyLoss, softmax Dice, DiceCE, GeneralizedDice): one kernel pair that knows none of them.
+ * x is fp32 (N, C, R) addressed by x_strides = (stride_n, stride_c, stride_r), as in pytc_bce_dice_fwd: a channels-last output, a
+ * plain NCDHW tensor or a channel slice of a wider tensor, uncopied.  2 <= C <= 32; another C returns PYTC_ERR_UNSUPPORTED.
+ * target_kind 0: dense fp32 (N, C, R) with t_strides; 1: class index as fp32 (N, R), truncated toward zero; 2: class index as int64
+ *   (N, R).  For 1 and 2 t_strides = (stride_n, unused, stride_r), t = onehot(y); a voxel with y == ignore_index is CE-invalid and has
+ *   t = 0 in every channel; any other label outside [0, C) traps nothing and writes NaN into column 5 of every class of its sample.
+ * mask: nullable fp32 (N, 1 or C, R) with m_strides (a channel stride of 0 broadcasts one channel).  Where mask <= 0 the logit reads
+ *   as `fill` and a dense target as 0; an index label reads as 0 unless every channel of its voxel is valid.  Masked voxels still count
+ *   in the sums (p = 1 / C where every channel is masked); dx is 0 at every masked element.
+ * Per voxel m = max_c x_c, lse = m + log sum_c exp(x_c - m), logp_c = x_c - lse, p_c = exp(x_c - m) / sum.
+ * pytc_softmax_loss_forward: sums[n][c][0..7] = the sums over the voxels of sample n of
+ *     p t,  p,  p^2,  t,  t^2,  valid t (-logp),  valid (-logp),  valid t          (valid = the voxel is CE-valid)
+ *   in fp32; partial = 8 N C pytc_softmax_loss_tiles(R) floats of per-tile sums that a second launch adds in a fixed order (no atomics:
+ *   two runs give the same bits).  Nothing per-voxel is saved.
+ * pytc_softmax_loss_backward: gsums (N, C, 8) = d L / d sums (columns 3, 4 and 7 are ignored); p is recomputed from the operands;
+ *   with u_k = g0_k t_k + g1_k + 2 g2_k p_k and h_k = valid (g5_k t_k + g6_k):
+ *     dx_c = p_c (u_c - sum_k p_k u_k) + (p_c sum_k h_k - h_c)
+ *   written through d_strides (dx may keep the logits' channels-last strides).  Nothing synchronises with the host. */
+int pytc_softmax_loss_tiles(int64_t R);
+int pytc_softmax_loss_forward(const float* x, const void* target, const float* mask, float* partial, float* sums, int N, int C, int64_t R,
+                              const int64_t* x_strides, const int64_t* t_strides, const int64_t* m_strides, int target_kind,
+                              int64_t ignore_index, float fill, void* stream);
+int pytc_softmax_loss_backward(const float* x, const void* target, const float* mask, const float* gsums, float* dx, int N, int C,
+                               int64_t R, const int64_t* x_strides, const int64_t* t_strides, const int64_t* m_strides,
+                               const int64_t* d_strides, int target_kind, int64_t ignore_index, float fill, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 9         # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 10        # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -309,6 +309,11 @@ _SIGS = {
     "pytc_scnp_tiles": (C.c_int, [C.c_int64]),
     "pytc_scnp_forward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p]),
     "pytc_scnp_backward": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 9 + [C.c_void_p]),
+    "pytc_softmax_loss_tiles": (C.c_int, [C.c_int64]),
+    "pytc_softmax_loss_forward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int64)] * 3
+                                  + [C.c_int, C.c_int64, C.c_float, C.c_void_p]),
+    "pytc_softmax_loss_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int64)] * 4
+                                   + [C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "pytc_reg_tiles": (C.c_int, [C.c_int64]),
     "pytc_reg_pointwise_forward": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "pytc_reg_pointwise_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),

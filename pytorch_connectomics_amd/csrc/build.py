@@ -26,7 +26,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-re
 # streams share a SIMD, so the compiler's SLP vectoriser -- the only source of v_pk_*_f32 in compiler-generated code -- is off)
 _NO_SLP = os.environ.get("PYTC_NO_SLP_FILES", "dwconv_kernels.hip,dwconv_mfma_kernels.hip,train_kernels.hip,rsunet_train_kernels.hip,"
                          "conv3d_strided_kernels.hip,loss_optim_kernels.hip,volume_kernels.hip,upcat_kernels.hip,transformer_kernels.hip,"
-                         "scnp_kernels.hip,regularization_kernels.hip")
+                         "scnp_kernels.hip,regularization_kernels.hip,softmax_loss_kernels.hip")
 EXTRA_FLAGS = {p.name: ["-fno-slp-vectorize"] for p in Path(__file__).resolve().parent.glob("*.hip")
                if _NO_SLP == "all" or p.name in _NO_SLP.split(",")}
 

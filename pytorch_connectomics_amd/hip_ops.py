@@ -2508,3 +2508,104 @@ def fgcontour_backward(coef: torch.Tensor, fg: torch.Tensor, contour: torch.Tens
     _run("fgcontour_backward", _nbytes(fg, contour, mask, code, dfg, dct), nat.lib().pytc_fgcontour_backward, _p(fg), _p(contour),
          _p(mask), _p(code), _p(coef), _p(dfg), _p(dct), N, D, H, W, float(eps), _stream())
     return dfg, dct
+
+
+# ---- softmax losses: the channel softmax reduced to eight sums per (sample, class), and its gradient (csrc/softmax_loss_kernels.hip) ----
+SOFTMAX_LOSS_MAX_C = 32
+
+
+def _ncr(t: torch.Tensor):
+    """(stride_n, stride_c, stride_r) of a (N, C, *spatial) tensor whose spatial dims collapse into one stride, else None.  Size-1
+    spatial dims carry no address information and are dropped first; the rest must nest, and stride_r is the last one's."""
+    dims = [(int(sh), int(st)) for sh, st in zip(t.shape[2:], t.stride()[2:]) if sh != 1]
+    for (_, st_outer), (sh_inner, st_inner) in zip(dims[:-1], dims[1:]):
+        if st_outer != st_inner * sh_inner:
+            return None
+    return (t.stride(0), t.stride(1), dims[-1][1] if dims else 1)
+
+
+def _strided(t: torch.Tensor):
+    """-> (the tensor, or a contiguous copy when its spatial dims do not collapse; its three strides as a C array)."""
+    s = _ncr(t)
+    if s is None or min(s) < 0:
+        t = t.contiguous()
+        s = _ncr(t)
+    return t, (C.c_int64 * 3)(*s)
+
+
+def _softmax_loss_operands(x: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor]):
+    """x fp32 (N, C, *spatial) in any layout whose spatial dims collapse; target dense fp32 of x's shape, or a class index of shape
+    (N, *spatial) as fp32 or int64; mask None or fp32 (N, 1 or C, *spatial).  -> operands, strides, target kind, N, C, R."""
+    for name, t in (("logits", x), ("target", target)) + ((("mask", mask),) if mask is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA(HIP) tensor: pytorch_connectomics_amd has no CPU path")
+    if x.dtype != torch.float32 or x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"logits must be non-empty float32 of shape (N, C, *spatial), got {x.dtype} {tuple(x.shape)}")
+    N, C_ = int(x.shape[0]), int(x.shape[1])
+    if not 2 <= C_ <= SOFTMAX_LOSS_MAX_C:
+        raise NotImplementedError(f"the softmax-loss kernels cover 2 <= C <= {SOFTMAX_LOSS_MAX_C} classes, got C = {C_} "
+                                  "(CPU tensors, or use_hip=False, take any C)")
+    R = x.numel() // (N * C_)
+    if target.shape == x.shape:
+        if target.dtype != torch.float32:
+            raise ValueError(f"a dense target must be float32, got {target.dtype}")
+        kind = 0
+        t, ts = _strided(target)
+    elif target.shape == x.shape[:1] + x.shape[2:]:
+        if target.dtype not in (torch.float32, torch.int64):
+            raise ValueError(f"a class-index target must be float32 or int64, got {target.dtype}")
+        kind = 1 if target.dtype == torch.float32 else 2
+        t, ts = _strided(target.unsqueeze(1))
+    else:
+        raise ValueError(f"target of shape {tuple(target.shape)} is neither dense {tuple(x.shape)} nor a class index "
+                         f"{tuple(x.shape[:1] + x.shape[2:])}")
+    x, xs = _strided(x)
+    m, ms = None, None
+    if mask is not None:
+        if mask.dtype != torch.float32 or mask.dim() != x.dim() or mask.shape[0] != N or mask.shape[1] not in (1, C_) \
+                or mask.shape[2:] != x.shape[2:]:
+            raise ValueError(f"mask must be float32 of shape {tuple(x.shape)} or with one channel, got {mask.dtype} {tuple(mask.shape)}")
+        m, ms = _strided(mask)
+        if mask.shape[1] == 1:
+            ms[1] = 0
+    return x, xs, t, ts, m, ms, kind, N, C_, R
+
+
+def softmax_loss_forward(x: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, *, ignore_index: int = -100,
+                         fill: float = -20.0, _buffers=None) -> torch.Tensor:
+    """-> sums (N, C, 8) fp32 of the channel softmax p of x against the target t (include/pytc_hip.h pytc_softmax_loss_forward):
+    p t, p, p^2, t, t^2, valid t (-logp), valid (-logp), valid t.  No copy of the logits, no atomics, no host synchronisation.
+    `_buffers` = (partial, sums) lets a test supply guarded allocations."""
+    x, xs, t, ts, m, ms, kind, N, C_, R = _softmax_loss_operands(x, target, mask)
+    lib = nat.lib()
+    n_part = 8 * N * C_ * lib.pytc_softmax_loss_tiles(R)
+    if _buffers is None:
+        part = torch.empty((n_part,), dtype=torch.float32, device=x.device)
+        sums = torch.empty((N, C_, 8), dtype=torch.float32, device=x.device)
+    else:
+        part, sums = _buffers
+        if part.numel() != n_part or sums.shape != (N, C_, 8) or not sums.is_contiguous():
+            raise ValueError(f"_buffers must hold {n_part} partials and contiguous sums of shape {(N, C_, 8)}")
+    _run(f"softmax_loss_forward[C={C_}]", _nbytes(x, t, m), lib.pytc_softmax_loss_forward, _p(x), _p(t), _p(m), _p(part), _p(sums), N, C_, R,
+         xs, ts, ms, kind, int(ignore_index), float(fill), _stream(), symbol="softmax_loss_forward")
+    return sums
+
+
+def softmax_loss_backward(gsums: torch.Tensor, x: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                          ignore_index: int = -100, fill: float = -20.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> dx of x's shape and (where they collapse) strides, from gsums (N, C, 8) = d loss / d sums; the softmax is recomputed."""
+    x, xs, t, ts, m, ms, kind, N, C_, R = _softmax_loss_operands(x, target, mask)
+    gsums = _dev(gsums.to(torch.float32).contiguous(), "gsums")
+    if gsums.shape != (N, C_, 8):
+        raise ValueError(f"gsums must have shape {(N, C_, 8)}, got {tuple(gsums.shape)}")
+    dx = torch.empty_like(x) if out is None else out
+    ds = _ncr(dx)
+    if out is None and (ds is None or min(ds) < 1):
+        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        ds = _ncr(dx)
+    if dx.shape != x.shape or dx.dtype != torch.float32 or ds is None or min(ds) < 1:
+        raise ValueError("out must be float32 of the logits' shape with collapsible, non-broadcast strides")
+    _run(f"softmax_loss_backward[C={C_}]", _nbytes(x, t, m) + dx.numel() * 4, nat.lib().pytc_softmax_loss_backward, _p(x), _p(t), _p(m),
+         _p(gsums), _p(dx), N, C_, R, xs, ts, ms, (C.c_int64 * 3)(*ds), kind, int(ignore_index), float(fill), _stream(),
+         symbol="softmax_loss_backward")
+    return dx

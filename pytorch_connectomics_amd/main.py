@@ -263,6 +263,9 @@ def run_train(cfg, args) -> dict:
         vol = torch.from_numpy(np.ascontiguousarray(normalize_image_for_config(read_volume(str(img_spec)), cfg), dtype=np.float32))
         lab = torch.from_numpy(np.ascontiguousarray(read_volume(str(cfg.data.train.label))).astype(np.float32))
         g = torch.Generator().manual_seed(int(cfg.system.seed) + rank)
+        # a class-index term (CrossEntropyLoss, or to_onehot_y of the softmax losses) reads the label volume's class numbers; every
+        # other configuration keeps the binary foreground target
+        keep_classes = any(t.get("target_kind") == "class_index" or bool(t["kwargs"].get("to_onehot_y", False)) for t in module.loss_terms)
 
         def sampler():
             while True:
@@ -273,7 +276,7 @@ def run_train(cfg, args) -> dict:
                     o = [int(torch.randint(0, vol.shape[a] - full[a] + 1, (1,), generator=g)) for a in range(vol.dim())]
                     sl = tuple(slice(o[a], o[a] + full[a]) for a in range(vol.dim()))
                     xv, yv = vol[sl].reshape(patch), lab[sl].reshape(patch)
-                    xs.append(xv[None]); ys.append((yv > 0).float()[None])
+                    xs.append(xv[None]); ys.append((yv if keep_classes else (yv > 0).float())[None])
                 yield {"image": torch.stack(xs), "label": torch.stack(ys)}
         batches = sampler()
     t0 = time.perf_counter()

@@ -24,6 +24,7 @@ from ..utils.model_outputs import resolve_head_target_slice, unwrap_main_output
 from .cldice_autograd import SoftClDiceLoss, soft_cldice_term
 from .regularization_autograd import REGULARIZATION_LOSSES
 from .scnp_autograd import ScnpLoss, scnp_term
+from .softmax_loss_autograd import SOFTMAX_LOSSES, check_softmax_dice_kwargs, softmax_dice_loss
 
 _NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d,
                nn.InstanceNorm2d, nn.InstanceNorm3d, nn.LayerNorm, nn.LocalResponseNorm)
@@ -249,6 +250,15 @@ _LOSSES = {
 # combined mask (models/losses/metadata.py:53-76).  A term holds its loss instance, built once with the module.
 _LOSSES.update({name: cls for name, (cls, _kind, _arg) in REGULARIZATION_LOSSES.items()})
 _CALL_KINDS = {name: (kind, arg) for name, (_cls, kind, arg) in REGULARIZATION_LOSSES.items()}     # every other loss: pred_target
+# the softmax losses and L1Loss (training/softmax_loss_autograd.py): no spatial weight argument; the term's mask reaches them -- and,
+# for the softmax ones, the HIP kernels -- as `mask` with fill = the clamp minimum, never as a masked_fill copy of the logits
+_LOSSES.update({name: fn for name, (fn, _check, _kind) in SOFTMAX_LOSSES.items()})            # called as fn(pred, target, mask, fill=, **kwargs)
+_TARGET_KINDS = {name: kind for name, (_fn, _check, kind) in SOFTMAX_LOSSES.items()}                # every other loss: dense
+
+
+def _is_softmax_dice(fn: str, kwargs) -> bool:
+    """A DiceLoss term takes the softmax path only when `softmax` or `to_onehot_y` is set; the sigmoid / plain form keeps its own."""
+    return fn == "DiceLoss" and bool(kwargs.get("softmax", False) or kwargs.get("to_onehot_y", False))
 
 
 def match_target_to_output(target: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
@@ -425,6 +435,10 @@ class ConnectomicsModule(nn.Module):
                 SoftClDiceLoss(**dict(get("kwargs", None) or {}))      # its argument checks run when the module is built, as there
             if fn == "ScnpLoss":
                 ScnpLoss(**dict(get("kwargs", None) or {}))
+            if fn in SOFTMAX_LOSSES:
+                SOFTMAX_LOSSES[fn][1](**dict(get("kwargs", None) or {}))
+            if _is_softmax_dice(fn, dict(get("kwargs", None) or {})):
+                check_softmax_dice_kwargs("DiceLoss", **dict(get("kwargs", None) or {}))
             # how the loss is called (training/losses/plan.py:158-237): the kind is the loss's own; a term may restate it
             where = f"losses[{len(self.loss_terms)}]"
             own_kind, spatial_arg = _CALL_KINDS.get(fn, ("pred_target", None))
@@ -472,6 +486,7 @@ class ConnectomicsModule(nn.Module):
                                     "pred_slice": pred_slice, "call_kind": call_kind, "pred2_slice": pred2_slice,
                                     "pred2_head": pred2_head, "spatial_arg": spatial_arg, "loss": loss_module,
                                     "target_slice": target_slice, "pos_weight": pos_weight,
+                                    "target_kind": _TARGET_KINDS.get(fn, "dense"),
                                     "mask_slice": get("mask_slice", get("mask")),
                                     "apply_deep_supervision": bool(get("apply_deep_supervision", True)),
                                     "kwargs": dict(get("kwargs", None) or {})})
@@ -499,6 +514,8 @@ class ConnectomicsModule(nn.Module):
         if t["fn"] not in self._FUSABLE or t.get("mask_slice") is not None:
             return False
         kw = t["kwargs"]
+        if _is_softmax_dice(t["fn"], kw):
+            return False
         if self._FUSABLE[t["fn"]] == "bce":
             return not isinstance(t["pos_weight"], str) and str(kw.get("reduction", "mean")) == "mean" and \
                 not (set(kw) - {"reduction"})
@@ -543,25 +560,31 @@ class ConnectomicsModule(nn.Module):
         plain_bce_masked = mask is not None and any(t["fn"] == "BCEWithLogitsLoss" for _, t in terms)
         return bool(pred.is_cuda and self.fused_loss and not plain_bce_masked and all(self._term_is_fusable(t, pred) for _, t in terms))
 
-    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None):
+    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None, full_labels=None):
         """Weighted sum of the loss terms `terms` (list of (index, term); default: all) on one prediction tensor.
         tasks: a dict that receives {term index: static weight x raw value, WITH its graph} (adaptive balancing: the caller
         combines the tasks); the fused kernel steps aside then -- it returns one scalar for all its terms.
-        heads: the named-head outputs, for a `pred_pred` term whose second slice comes from another head."""
+        heads: the named-head outputs, for a `pred_pred` term whose second slice comes from another head.
+        full_labels: on a deep-supervision scale, the labels at full resolution: a `class_index` term (CrossEntropyLoss) resizes ITS
+        channel of them by nearest neighbour (orchestrator.py:277-291, 578-586) instead of reading the densely resized `target`."""
         terms = list(enumerate(self.loss_terms)) if terms is None else terms
         pred = torch.clamp(pred, min=self.clamp_min, max=self.clamp_max)
         total, parts = 0.0, {}
         if tasks is None:
             # the terms without a target (regularisers) never enter the fused reduction and must not push the supervised terms off
             # it: those are judged on their own, the rest is added below
-            supervised = [(i, t) for i, t in terms if t.get("call_kind", "pred_target") == "pred_target"]
+            # (nor do the softmax losses and L1Loss, which have kernels or rows of their own)
+            def on_fused(t):
+                return t.get("call_kind", "pred_target") == "pred_target" and t["fn"] not in SOFTMAX_LOSSES \
+                    and not _is_softmax_dice(t["fn"], t["kwargs"])
+            supervised = [(i, t) for i, t in terms if on_fused(t)]
             if supervised and self._fusable(pred, mask, supervised):
                 res = self._fused_term_loss(pred, target, mask, supervised)      # finiteness is checked where fit() reads the value
                 if res is not None:
                     if len(supervised) == len(terms):
                         return res
                     total, parts = res
-                    terms = [(i, t) for i, t in terms if t.get("call_kind", "pred_target") != "pred_target"]
+                    terms = [(i, t) for i, t in terms if not on_fused(t)]
         for i, t in terms:
             if t.get("call_kind", "pred_target") != "pred_target":
                 v = self._regularizer_loss(i, t, pred, target, mask, heads)
@@ -573,8 +596,15 @@ class ConnectomicsModule(nn.Module):
             p, y = pred, target
             if t["pred_slice"] is not None:
                 p = pred[:, resolve_channel_indices(t["pred_slice"], num_channels=pred.shape[1], context="pred_slice")]
+            if t.get("target_kind", "dense") == "class_index" and full_labels is not None:
+                y = full_labels
             if t["target_slice"] is not None:
-                y = target[:, resolve_channel_indices(t["target_slice"], num_channels=target.shape[1], context="target_slice")]
+                y = y[:, resolve_channel_indices(t["target_slice"], num_channels=y.shape[1], context="target_slice")]
+            if t.get("target_kind", "dense") == "class_index":
+                if y.dim() != pred.dim() or y.shape[1] != 1:
+                    raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' takes a class-index target of one channel, got "
+                                     f"{tuple(y.shape)} (name it with target_slice)")
+                y = resize_class_index_to_output(y, pred)
             # what the loss sees as its spatial argument (reference orchestrator.py:566-646): a term's own mask channels
             # (`mask_slice` of the labels) x the batch mask; a `weight`-taking loss without a mask of its own gets the
             # class-balancing map instead (not the weighted BCE, whose pos_weight is a scalar of its own)
@@ -596,6 +626,11 @@ class ConnectomicsModule(nn.Module):
                 elif pw is not None and float(pw) == 1.0:
                     pw = None
                 v = _LOSSES[fn](p, y, weight=spatial, pos_weight=pw, clamp_min=self.clamp_min, **t["kwargs"])
+            elif _is_softmax_dice(fn, t["kwargs"]):
+                v = softmax_dice_loss(p, y, valid, fill=self.clamp_min, **t["kwargs"])
+            elif fn in SOFTMAX_LOSSES:
+                # the mask goes by position: `weight` in the term's kwargs is the CLASS weight of CrossEntropyLoss / DiceCELoss
+                v = _LOSSES[fn](p, y, valid, fill=self.clamp_min, **t["kwargs"])
             else:
                 v = _LOSSES[fn](p, y, weight=valid, pos_weight=None, clamp_min=self.clamp_min, **t["kwargs"])
             if not torch.isfinite(v):
@@ -632,7 +667,7 @@ class ConnectomicsModule(nn.Module):
             raise FloatingPointError(f"loss term {t['fn']} is not finite")
         return v
 
-    def _balanced_scale_loss(self, items, stage: str, heads=None):
+    def _balanced_scale_loss(self, items, stage: str, heads=None, full_labels=None):
         """One output scale under adaptive loss balancing (orchestrator.py:110-127, 779-790): `items` = [(pred, target, mask, terms)]
         (one entry per head); every term is a task whose loss is its static weight x raw value, the weighter combines ALL tasks of
         the scale in one call.  Uncertainty weighting on fusable terms keeps the fused HIP loss: the per-task coefficients
@@ -675,7 +710,7 @@ class ConnectomicsModule(nn.Module):
             parts = {}
         tasks: Dict[int, torch.Tensor] = {}
         for pred, target, mask, terms in items:
-            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks, heads=heads)
+            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks, heads=heads, full_labels=full_labels)
             parts.update(pr)
         total, wts, logs = w.combine([tasks[i] for i in idx], names, stage)
         for n, wt in zip(names, wts):
@@ -749,9 +784,9 @@ class ConnectomicsModule(nn.Module):
                 if not on_scales:
                     continue
                 if self.loss_weighter is not None:
-                    li, _ = self._balanced_scale_loss([(ds, tgt, m, on_scales)], stage)
+                    li, _ = self._balanced_scale_loss([(ds, tgt, m, on_scales)], stage, full_labels=labels)
                 else:
-                    li, _ = self._term_loss(ds, tgt, m, on_scales)
+                    li, _ = self._term_loss(ds, tgt, m, on_scales, full_labels=labels)
                 total = total + self.ds_weights[i] * li
         parts["train_loss_total"] = total.detach()
         return total, parts
