@@ -15,7 +15,17 @@
 //                      the window's statistics from a fixed-order two-stage reduction in fp64.
 #include "pytc_common.h"
 
+// One rounding per operation.  HIP's __fmul_rn / __fadd_rn are plain operators defined in a header, compiled with the header's
+// contraction setting: inlined here, each `a * (1 - f) + b * f` of the trilinear blend became a multiply and an FMA (the second
+// product unrounded), and the fp64 variance `q / n - mean * mean` one FMA.  Contraction is off for this file and the rounded fp32
+// operations are the operators below, written under that setting.
+#pragma clang fp contract(off)
+
 namespace pytc {
+
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 
 template <typename T>
 __device__ __forceinline__ float raw_to_f32(T v) { return (float)v; }
@@ -56,13 +66,13 @@ resample_region_kernel(const T* __restrict__ raw, long sc, long sz, long sy, lon
     } else {
       // separable trilinear blend; weights (1 - f, f) per axis as torch's grid_sample forms them (align_corners=True)
       const float gx0 = 1.f - fx, gy0 = 1.f - fy, gz0 = 1.f - fz;
-      const float r00 = __fadd_rn(__fmul_rn(raw_to_f32(p[a00 + b0]), gx0), __fmul_rn(raw_to_f32(p[a00 + b1]), fx));
-      const float r01 = __fadd_rn(__fmul_rn(raw_to_f32(p[a01 + b0]), gx0), __fmul_rn(raw_to_f32(p[a01 + b1]), fx));
-      const float r10 = __fadd_rn(__fmul_rn(raw_to_f32(p[a10 + b0]), gx0), __fmul_rn(raw_to_f32(p[a10 + b1]), fx));
-      const float r11 = __fadd_rn(__fmul_rn(raw_to_f32(p[a11 + b0]), gx0), __fmul_rn(raw_to_f32(p[a11 + b1]), fx));
-      const float q0 = __fadd_rn(__fmul_rn(r00, gy0), __fmul_rn(r01, fy));
-      const float q1 = __fadd_rn(__fmul_rn(r10, gy0), __fmul_rn(r11, fy));
-      v = __fadd_rn(__fmul_rn(q0, gz0), __fmul_rn(q1, fz));
+      const float r00 = add_rn(mul_rn(raw_to_f32(p[a00 + b0]), gx0), mul_rn(raw_to_f32(p[a00 + b1]), fx));
+      const float r01 = add_rn(mul_rn(raw_to_f32(p[a01 + b0]), gx0), mul_rn(raw_to_f32(p[a01 + b1]), fx));
+      const float r10 = add_rn(mul_rn(raw_to_f32(p[a10 + b0]), gx0), mul_rn(raw_to_f32(p[a10 + b1]), fx));
+      const float r11 = add_rn(mul_rn(raw_to_f32(p[a11 + b0]), gx0), mul_rn(raw_to_f32(p[a11 + b1]), fx));
+      const float q0 = add_rn(mul_rn(r00, gy0), mul_rn(r01, fy));
+      const float q1 = add_rn(mul_rn(r10, gy0), mul_rn(r11, fy));
+      v = add_rn(mul_rn(q0, gz0), mul_rn(q1, fz));
     }
     out[(long)c * total + i] = v;
   }
@@ -148,8 +158,8 @@ window_apply_kernel(float* __restrict__ x, long n, int B, int binarize, float th
     const int b = (int)(i / n);
     float v = prep_value(x[i], binarize, thr, clip, b);
     if (mode == PYTC_NORM_DIVIDE) v = __fdiv_rn(v, divide);
-    else if (mode == PYTC_NORM_ZSCORE) v = __fmul_rn(__fsub_rn(v, coef[2 * b]), coef[2 * b + 1]);
-    else if (mode == PYTC_NORM_MINMAX) v = __fmul_rn(__fsub_rn(v, coef[2 * b]), coef[2 * b + 1]);
+    else if (mode == PYTC_NORM_ZSCORE) v = mul_rn(sub_rn(v, coef[2 * b]), coef[2 * b + 1]);
+    else if (mode == PYTC_NORM_MINMAX) v = mul_rn(sub_rn(v, coef[2 * b]), coef[2 * b + 1]);
     x[i] = v;
   }
 }

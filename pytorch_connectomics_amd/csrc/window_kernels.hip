@@ -4,7 +4,17 @@
 // so the fp32 accumulation order is exactly the reference's window order).
 #include "pytc_common.h"
 
+// One rounding per operation.  HIP's __fmul_rn / __fadd_rn are plain operators defined in a header, compiled with the header's
+// contraction setting: inlined here, `value + pred * w` became one FMA (one rounding) where the reference rounds the product and the
+// sum separately, and fl16(x * scale) one fused conversion.  Contraction is off for this file and the rounded operations are the
+// operators below, written under that setting.
+#pragma clang fp contract(off)
+
 namespace pytc {
+
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
 
 struct StartList {
   int s[64 * 3];
@@ -126,7 +136,7 @@ blend_accumulate_kernel(const TP* __restrict__ pred, int sz, int sy, int sx, int
     w = fminf(fminf(wzv[wz], wyv[wy]), wxv[wx]);
   } else {
     // (wz*wy)*wx, each product rounded (axis order of window.py:178-194), then the two floors
-    w = __fmul_rn(__fmul_rn(wzv[wz], wyv[wy]), wxv[wx]);
+    w = mul_rn(mul_rn(wzv[wz], wyv[wy]), wxv[wx]);
     w = fmaxf(w, 1.17549435e-38f);
     w = fmaxf(w, floor_w);
   }
@@ -139,9 +149,9 @@ blend_accumulate_kernel(const TP* __restrict__ pred, int sz, int sy, int sx, int
   for (int c = 0; c < C; ++c) {
     float pv = to_f32<TP>(p[c]);
     // separate multiply and add roundings: value += pred * w  (window.py:652-654)
-    value[c * plane + dst] = __fadd_rn(value[c * plane + dst], __fmul_rn(pv, w));
+    value[c * plane + dst] = add_rn(value[c * plane + dst], mul_rn(pv, w));
   }
-  if (weight) weight[dst] = __fadd_rn(weight[dst], w);
+  if (weight) weight[dst] = add_rn(weight[dst], w);
 }
 
 // ---- affinity-aware blending (inference/tta_affinity.py:350-393 fused into the scatter) ------------------------------
@@ -158,7 +168,7 @@ __device__ __forceinline__ float window_weight(const float* wzv, const float* wy
   if (combine == PYTC_BLEND_MIN) {
     w = fminf(fminf(wzv[z], wyv[y]), wxv[x]);
   } else {
-    w = __fmul_rn(__fmul_rn(wzv[z], wyv[y]), wxv[x]);
+    w = mul_rn(mul_rn(wzv[z], wyv[y]), wxv[x]);
     w = fmaxf(w, 1.17549435e-38f);
     w = fmaxf(w, floor_w);
   }
@@ -189,13 +199,13 @@ blend_accumulate_mapped_kernel(const TP* __restrict__ pred, int sz, int sy, int 
     if (gz < 0 || gz >= Z || gy < 0 || gy >= Y || gx < 0 || gx >= X) continue;
     const float w = window_weight(wzv, wyv, wxv, combine, floor_w, pz, py, px, rz, ry, rx, bz, by, bx);
     const long dst = ((long)gz * Y + gy) * X + gx;
-    value[d * plane + dst] = __fadd_rn(value[d * plane + dst], __fmul_rn(to_f32<TP>(p[m.src[d]]), w));
+    value[d * plane + dst] = add_rn(value[d * plane + dst], mul_rn(to_f32<TP>(p[m.src[d]]), w));
   }
   if (weight) {
     const int gz = sz + qz, gy = sy + qy, gx = sx + qx;
     if (gz >= 0 && gz < Z && gy >= 0 && gy < Y && gx >= 0 && gx < X) {
       const long dst = ((long)gz * Y + gy) * X + gx;
-      weight[dst] = __fadd_rn(weight[dst], window_weight(wzv, wyv, wxv, combine, floor_w, qz, qy, qx, rz, ry, rx, bz, by, bx));
+      weight[dst] = add_rn(weight[dst], window_weight(wzv, wyv, wxv, combine, floor_w, qz, qy, qx, rz, ry, rx, bz, by, bx));
     }
   }
 }
@@ -216,7 +226,7 @@ blend_weight_shifted_kernel(int sz, int sy, int sx, int rz, int ry, int rx, cons
   const int gz = sz + pz, gy = sy + py, gx = sx + px;
   if (gz < 0 || gz >= Z || gy < 0 || gy >= Y || gx < 0 || gx >= X) return;
   const long dst = ((long)gz * Y + gy) * X + gx;
-  weight[dst] = __fadd_rn(weight[dst], window_weight(wzv, wyv, wxv, combine, floor_w, pz, py, px, rz, ry, rx, bz, by, bx));
+  weight[dst] = add_rn(weight[dst], window_weight(wzv, wyv, wxv, combine, floor_w, pz, py, px, rz, ry, rx, bz, by, bx));
 }
 
 // v = w > 0 ? v / w : 0   (tta.py:1238-1244: partial channels are normalised by their own coverage, unclamped)
@@ -237,7 +247,7 @@ ensemble_update_masked_kernel(float* __restrict__ stat, float* __restrict__ coun
     if (cover && !(cover[i] > 0.f)) continue;
     const float v = x[i];
     float a = stat[i];
-    a = mode == 0 ? __fadd_rn(a, v) : (mode == 1 ? fminf(a, v) : fmaxf(a, v));
+    a = mode == 0 ? add_rn(a, v) : (mode == 1 ? fminf(a, v) : fmaxf(a, v));
     stat[i] = a;
     count[i] = count[i] + 1.f;
   }
@@ -275,7 +285,7 @@ ensemble_update_kernel(float* __restrict__ acc, const float* __restrict__ x, lon
   for (; i < n; i += stride) {
     float a = acc[i], v = x[i];
     if (count <= 1) a = v;
-    else if (mode == 0) a = __fadd_rn(a, __fdiv_rn(__fsub_rn(v, a), (float)count));
+    else if (mode == 0) a = add_rn(a, __fdiv_rn(sub_rn(v, a), (float)count));
     else if (mode == 1) a = fminf(a, v);
     else a = fmaxf(a, v);
     acc[i] = a;
@@ -451,8 +461,11 @@ extern "C" int pytc_blend_weight_shifted(int B, const int32_t* starts, int rz, i
                                          const int32_t* border, const int32_t* shift, float* weight, int Z, int Y, int X,
                                          void* stream) {
   PYTC_REQUIRE(starts && wz && wy && wx && shift && weight && B >= 1, "blend_weight_shifted: bad arguments");
+  PYTC_REQUIRE(combine == PYTC_BLEND_PRODUCT || combine == PYTC_BLEND_MIN, "blend_weight_shifted: bad combine");
   const long per_win = (long)rz * ry * rx;
   const int bz = border ? border[0] : 0, by = border ? border[1] : 0, bx = border ? border[2] : 0;
+  PYTC_REQUIRE(bz >= 0 && by >= 0 && bx >= 0 && 2 * bz < rz && 2 * by < ry && 2 * bx < rx,
+               "blend_weight_shifted: border mask too large for the window");
   for (int b = 0; b < B; ++b)
     hipLaunchKernelGGL(blend_weight_shifted_kernel, dim3(ceil_div(per_win, 256)), dim3(256), 0, (hipStream_t)stream,
                        starts[3 * b], starts[3 * b + 1], starts[3 * b + 2], rz, ry, rx, wz, wy, wx, combine, floor_w, bz, by, bx,
@@ -516,7 +529,10 @@ scale_cast_kernel(const float* __restrict__ x, TO* __restrict__ y, long n, float
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float u = __fmul_rn(v[j], scale);
+      float u = mul_rn(v[j], scale);
+      // fp16 target: the backend folds fpround(fmul) into one v_fma_mixlo_f16 (ONE rounding of the exact product) whatever the
+      // contraction setting; numpy rounds the fp32 product and then the cast.  The empty asm keeps the fp32 product a value of its own
+      if (sizeof(TO) == 2 && !INTEGER) asm volatile("" : "+v"(u));
       if (INTEGER) u = fminf(fmaxf(u, lo), hi);       // np.clip, then astype truncates toward zero
       if (i + j < n) y[i + j] = (TO)u;
     }

@@ -29,9 +29,14 @@ def require_device(device, what: str = "this inference path") -> None:
         raise RuntimeError(f"{what} (pytorch_connectomics_amd) needs a CUDA(HIP) device: there is no CPU path")
 
 
-def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
+def _on_device(t: torch.Tensor, name: str) -> torch.Tensor:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA(HIP) tensor: pytorch_connectomics_amd has no CPU path")
+    return t
+
+
+def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
+    _on_device(t, name)
     if not t.is_contiguous():
         raise RuntimeError(f"{name} must be contiguous")
     return t
@@ -129,6 +134,26 @@ def _starts_array(starts: Sequence[Sequence[int]], windows: Optional[int] = None
     return (C.c_int32 * len(flat))(*flat)
 
 
+def _f32_operand(t, name: str, *, shape=None, numel: Optional[int] = None) -> None:
+    """A float32, contiguous device operand of the given shape / size, or ValueError.  The kernels get raw pointers and index them
+    from their other arguments, so a short or strided operand would be read or written out of bounds on the device.  Attribute
+    comparisons only (the window loop is launch bound): no synchronisation, no new tensors."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 CUDA(HIP) tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must have {numel} elements, got {t.numel()}")
+
+
+def _window_operands(name: str, roi, weight, wshape, wz, wy, wx) -> None:
+    """the per-axis blending vectors (one entry per window position along the axis) and the weight accumulator of a blend"""
+    for t, n, ax in ((wz, roi[0], "wz"), (wy, roi[1], "wy"), (wx, roi[2], "wx")):
+        _f32_operand(t, f"{name}: {ax}", shape=(int(n),))
+    if weight is not None:
+        _f32_operand(weight, f"{name}: weight", shape=wshape)
+
+
 # ------------------------------------------------------------------ sliding window
 def gather_windows(vol: torch.Tensor, starts, roi, *, view: int = 0, pad_mode: str = "constant",
                    cval: float = 0.0, out_dtype: torch.dtype = torch.float32,
@@ -142,6 +167,9 @@ def gather_windows(vol: torch.Tensor, starts, roi, *, view: int = 0, pad_mode: s
     rz, ry, rx = (int(v) for v in roi)
     if out is None:
         out = torch.empty((B, rz, ry, rx, Cc), dtype=out_dtype, device=vol.device)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or not out.is_contiguous() or out.dtype not in _DT
+          or tuple(out.shape) != (B, rz, ry, rx, Cc)):
+        raise ValueError(f"gather_windows: out must be a contiguous float32 / bfloat16 CUDA(HIP) tensor of shape {(B, rz, ry, rx, Cc)}")
     st = _starts_array(starts)
     for b0 in range(0, B, 64):
         nb = min(64, B - b0)
@@ -162,6 +190,7 @@ def blend_accumulate(pred: torch.Tensor, starts, value: torch.Tensor, weight: Op
     if value.dtype != torch.float32 or value.shape[0] != Cc:
         raise ValueError("value accumulator must be float32 (C, Z, Y, X) with C matching pred")
     _, Z, Y, X = value.shape
+    _window_operands("blend_accumulate", (rz, ry, rx), weight, (Z, Y, X), wz, wy, wx)
     st = _starts_array(starts, B)
     bd = (C.c_int32 * 3)(*[int(v) for v in border]) if border else None
     win = B * rz * ry * rx
@@ -182,6 +211,7 @@ def blend_accumulate_mapped(pred: torch.Tensor, starts, value: torch.Tensor, wei
     if len(chan_src) != Cc or len(chan_shift) != Cc:
         raise ValueError("channel map must describe every output channel")
     _, Z, Y, X = value.shape
+    _window_operands("blend_accumulate_mapped", (rz, ry, rx), weight, (Z, Y, X), wz, wy, wx)
     st = _starts_array(starts, B)
     bd = (C.c_int32 * 3)(*[int(v) for v in border]) if border else None
     cs = (C.c_int32 * Cc)(*[int(v) for v in chan_src])
@@ -195,8 +225,11 @@ def blend_accumulate_mapped(pred: torch.Tensor, starts, value: torch.Tensor, wei
 def blend_weight_shifted(starts, roi, weight: torch.Tensor, wz, wy, wx, shift, *, combine: int = nat.BLEND_PRODUCT,
                          floor_w: float = 1e-5, border=None) -> None:
     """weight (Z,Y,X) += blending map over the box a window displaced by `shift` covers (per window, in order)."""
-    _dev(weight, "weight")
+    _on_device(weight, "weight")
+    if weight.dim() != 3 or len(roi) != 3 or len(shift) != 3:
+        raise ValueError("blend_weight_shifted: weight must be (Z, Y, X), roi and shift three integers")
     Z, Y, X = weight.shape
+    _window_operands("blend_weight_shifted", roi, weight, (Z, Y, X), wz, wy, wx)
     st = _starts_array(starts)
     B = len(starts)
     bd = (C.c_int32 * 3)(*[int(v) for v in border]) if border else None
@@ -217,21 +250,29 @@ def normalize_covered(value: torch.Tensor, weight: torch.Tensor) -> None:
 
 def ensemble_update_masked(stat: torch.Tensor, count: torch.Tensor, x: torch.Tensor, cover: Optional[torch.Tensor],
                            mode: int) -> None:
-    _dev(stat, "stat"); _dev(x, "x")
+    n = stat.numel()
+    for t, name in ((stat, "stat"), (count, "count"), (x, "x")) + (((cover, "cover"),) if cover is not None else ()):
+        _on_device(t, name)                                       # a host tensor: the package's RuntimeError; anything else: ValueError
+        _f32_operand(t, f"ensemble_update_masked: {name}", numel=n)
     _run("ensemble_update_masked", 3 * _nbytes(stat) + 2 * _nbytes(count), nat.lib().pytc_ensemble_update_masked, _p(stat),
          _p(count), _p(x), _p(cover), stat.numel(), int(mode), _stream())
 
 
 def ensemble_finalize_masked(stat: torch.Tensor, count: torch.Tensor, out: torch.Tensor, mode: int) -> None:
-    _dev(stat, "stat"); _dev(out, "out")
+    n = stat.numel()
+    for t, name in ((stat, "stat"), (count, "count"), (out, "out")):
+        _on_device(t, name)
+        _f32_operand(t, f"ensemble_finalize_masked: {name}", numel=n)
     _run("ensemble_finalize_masked", 3 * _nbytes(stat), nat.lib().pytc_ensemble_finalize_masked, _p(stat), _p(count), _p(out),
          stat.numel(), int(mode), _stream())
 
 
 def blend_finalize(value: torch.Tensor, weight: torch.Tensor, *, clamp: float = 1e-4, act: int = nat.ACT_NONE) -> None:
-    _dev(value, "value"); _dev(weight, "weight")
+    _on_device(value, "value"); _on_device(weight, "weight")
     Cc = value.shape[0]
     nvox = weight.numel()
+    _f32_operand(weight, "blend_finalize: weight")
+    _f32_operand(value, "blend_finalize: value", numel=Cc * nvox)
     _run("blend_finalize", 2 * _nbytes(value) + _nbytes(weight), nat.lib().pytc_blend_finalize, _p(value),
          _p(weight), Cc, nvox, float(clamp), int(act), _stream())
 
@@ -249,7 +290,9 @@ def channel_activation(value: torch.Tensor, c0: int, c1: int, act: int, scale: f
 
 
 def ensemble_update(acc: torch.Tensor, x: torch.Tensor, mode: int, count: int) -> None:
-    _dev(acc, "acc"); _dev(x, "x")
+    _on_device(acc, "acc"); _on_device(x, "x")
+    _f32_operand(acc, "ensemble_update: acc")
+    _f32_operand(x, "ensemble_update: x", numel=acc.numel())
     _run("ensemble_update", 2 * _nbytes(acc) + _nbytes(x), nat.lib().pytc_ensemble_update, _p(acc), _p(x),
          acc.numel(), int(mode), int(count), _stream())
 

@@ -1,9 +1,9 @@
 """Lazy sliding-window inference with per-window test-time augmentation and a mask volume (reference inference/lazy.py:986-1258:
 its loop hands every window batch to a TTAPredictor) -- the host orchestration on the CPU.
 
-The product has no CPU path, so the kernel module (`hip_ops`) is replaced by the small torch stand-ins below (test infrastructure,
-same idea as tests/test_host_distributed_inference.py): window gather with the reader's outer padding, blending, activations, the
-ensemble update.  Everything above the kernels -- which views run, inverse views, activation-before-ensemble order, per-channel
+The product has no CPU path, so the kernel module (`hip_ops`) is replaced by the CPU model of the kernels in
+tests/window_kernel_model.py (test infrastructure; the device kernels are held to the same model bit for bit in
+tests/test_gpu_window_exact.py): window gather with the reader's outer padding, blending, activations, the ensemble update.  Everything above the kernels -- which views run, inverse views, activation-before-ensemble order, per-channel
 ensemble modes, mask application, channel selection, blending of the ensembled windows -- is the product code, checked against
 tests/golden/lazy_tta.npz, the output of the REFERENCE's own lazy loop on the same volume / mask / network.  The same fixtures
 meet the real kernels in tests/test_gpu_lazy_chunked.py."""
@@ -12,151 +12,7 @@ import pytest
 import torch
 
 from lazy_tta_cases import LAZY_TTA_CASES, lazy_tta_cfg
-from test_host_distributed_inference import _CpuOps
-
-
-class _Ops(_CpuOps):
-    @staticmethod
-    def _gather_plain(vol, starts, roi, pad_mode="constant", cval=0.0, **_kw):
-        """(C,Z,Y,X) -> (B, *roi, C); a window overhanging the box is padded like np.pad (constant / reflect / replicate)."""
-        mode = {"constant": "constant", "reflect": "reflect", "replicate": "edge", "edge": "edge"}[str(pad_mode)]
-        ext = vol.shape[1:]
-        out = []
-        for s in starts:
-            lo = [max(0, s[a]) for a in range(3)]
-            hi = [min(ext[a], s[a] + roi[a]) for a in range(3)]
-            inner = vol[:, lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]].numpy()
-            pads = [(0, 0)] + [(lo[a] - s[a], s[a] + roi[a] - hi[a]) for a in range(3)]
-            kw = dict(constant_values=float(cval)) if mode == "constant" else {}
-            out.append(torch.from_numpy(np.pad(inner, pads, mode=mode, **kw)).permute(1, 2, 3, 0))
-        return torch.stack(out).contiguous()
-
-    # ---- TTA view codes, affinity channel maps (csrc/window_kernels.hip: view_src, blend_accumulate[_mapped], blend_weight_shifted) ----
-    @staticmethod
-    def _to_view(win, view):
-        """canonical window (..., z, y, x, C) -> the view the network sees: out[z, y, x] = win[T(F(z, y, x))]."""
-        from pytorch_connectomics_amd import _native as nat
-        if view & nat.VIEW_SWAP_YX:
-            win = win.transpose(-3, -2)
-        dims = [d for d, bit in ((-4, nat.VIEW_FLIP_Z), (-3, nat.VIEW_FLIP_Y), (-2, nat.VIEW_FLIP_X)) if view & bit]
-        return torch.flip(win, dims) if dims else win
-
-    @staticmethod
-    def _from_view(pred, view):
-        """prediction of a view (..., z, y, x, C) -> canonical window frame (the inverse of `_to_view`)."""
-        from pytorch_connectomics_amd import _native as nat
-        dims = [d for d, bit in ((-4, nat.VIEW_FLIP_Z), (-3, nat.VIEW_FLIP_Y), (-2, nat.VIEW_FLIP_X)) if view & bit]
-        pred = torch.flip(pred, dims) if dims else pred
-        return pred.transpose(-3, -2) if view & nat.VIEW_SWAP_YX else pred
-
-    @staticmethod
-    def _window_map(wz, wy, wx, combine, floor_w, border):
-        from pytorch_connectomics_amd.inference.window import _combine_axes
-        w = _combine_axes([wz, wy, wx], combine, floor_w, "cpu", torch.float32).clone()
-        if border is not None and any(int(b) for b in border):
-            keep = torch.zeros_like(w)
-            bz, by, bx = (int(b) for b in border)
-            keep[bz:w.shape[0] - bz, by:w.shape[1] - by, bx:w.shape[2] - bx] = 1.0
-            w = w * keep
-        return w
-
-    @staticmethod
-    def _land(dst, src, start, lo=(0, 0, 0)):
-        """dst[start + lo ...] += src, clipped to dst (voxels of a window outside the accumulator are skipped)."""
-        ext, size = dst.shape[-3:], src.shape[-3:]
-        a = [start[i] + lo[i] for i in range(3)]
-        l = [max(0, a[i]) for i in range(3)]
-        h = [min(ext[i], a[i] + size[i]) for i in range(3)]
-        if any(h[i] <= l[i] for i in range(3)):
-            return
-        d = tuple(slice(l[i], h[i]) for i in range(3))
-        s_ = tuple(slice(l[i] - a[i], h[i] - a[i]) for i in range(3))
-        dst[(Ellipsis,) + d] += src[(Ellipsis,) + s_]
-
-    @classmethod
-    def gather_windows(cls, vol, starts, roi, *, view=0, pad_mode="constant", cval=0.0, **_kw):  # noqa: F811  (view-aware form)
-        return cls._to_view(cls._gather_plain(vol, starts, roi, pad_mode=pad_mode, cval=cval), view).contiguous()
-
-    @classmethod
-    def blend_accumulate(cls, pred, starts, value, weight, wz, wy, wx, *, view=0, combine=0, floor_w=1e-5, border=None):
-        assert len(starts) == pred.shape[0]
-        w = cls._window_map(wz, wy, wx, combine, floor_w, border)
-        canon = cls._from_view(pred.float(), view)
-        for i, s in enumerate(starts):
-            cls._land(value, canon[i].permute(3, 0, 1, 2) * w, s)
-            if weight is not None:
-                cls._land(weight, w, s)
-
-    @classmethod
-    def blend_accumulate_mapped(cls, pred, starts, value, weight, wz, wy, wx, chan_src, chan_shift, *, view=0, combine=0, floor_w=1e-5,
-                                border=None):
-        """output channel d <- canonical prediction channel chan_src[d] displaced by chan_shift[d]: the value predicted at q lands
-        at p = q + shift, weighted by the window map at p; p outside the window is dropped."""
-        assert len(starts) == pred.shape[0]
-        w = cls._window_map(wz, wy, wx, combine, floor_w, border)
-        canon = cls._from_view(pred.float(), view)
-        roi = canon.shape[1:4]
-        for i, s in enumerate(starts):
-            for d, (src, sh) in enumerate(zip(chan_src, chan_shift)):
-                q_lo = [max(0, -int(sh[a])) for a in range(3)]
-                q_hi = [min(roi[a], roi[a] - int(sh[a])) for a in range(3)]
-                if any(q_hi[a] <= q_lo[a] for a in range(3)):
-                    continue
-                q = tuple(slice(q_lo[a], q_hi[a]) for a in range(3))
-                p_lo = [q_lo[a] + int(sh[a]) for a in range(3)]
-                pbox = tuple(slice(p_lo[a], p_lo[a] + q_hi[a] - q_lo[a]) for a in range(3))
-                cls._land(value[d], canon[i][q + (int(src),)] * w[pbox], s, p_lo)
-            if weight is not None:
-                cls._land(weight, w, s)
-
-    @classmethod
-    def blend_weight_shifted(cls, starts, roi, weight, wz, wy, wx, shift, *, combine=0, floor_w=1e-5, border=None):
-        """weight += the window map over the positions p of each window whose source p - shift lies inside the window."""
-        w = cls._window_map(wz, wy, wx, combine, floor_w, border)
-        p_lo = [max(0, int(shift[a])) for a in range(3)]
-        p_hi = [min(int(roi[a]), int(roi[a]) + int(shift[a])) for a in range(3)]
-        if any(p_hi[a] <= p_lo[a] for a in range(3)):
-            return
-        box = tuple(slice(p_lo[a], p_hi[a]) for a in range(3))
-        for s in starts:
-            cls._land(weight, w[box], s, p_lo)
-
-    @staticmethod
-    def normalize_covered(value, weight):
-        value.copy_(torch.where(weight > 0, value / torch.where(weight > 0, weight, torch.ones_like(weight)), torch.zeros_like(value)))
-
-    @staticmethod
-    def channel_activation(value, c0, c1, act, scale=1.0, *, channels_last=False):
-        from pytorch_connectomics_amd import _native as nat
-        v = value[..., c0:c1] if channels_last else value[c0:c1]
-        if act == nat.ACT_SIGMOID:
-            v.copy_(torch.sigmoid(scale * v))
-        elif act == nat.ACT_TANH:
-            v.copy_(torch.tanh(scale * v))
-        elif act == nat.ACT_SOFTMAX:
-            v.copy_(torch.softmax(v, dim=-1 if channels_last else 0))
-        else:
-            raise AssertionError(act)
-
-
-    @staticmethod
-    def ensemble_update_masked(stat, count, x, cover, mode):
-        """validity-aware streaming ensemble (csrc/window_kernels.hip pytc_ensemble_update_masked): only covered voxels contribute;
-        mean keeps a running sum, min / max the extreme; `count` the number of contributions."""
-        from pytorch_connectomics_amd.inference.tta import _MODE_CODE
-        inside = torch.ones_like(x, dtype=torch.bool) if cover is None else cover > 0
-        if mode == _MODE_CODE["mean"]:
-            stat += torch.where(inside, x, torch.zeros_like(x))
-        elif mode == _MODE_CODE["min"]:
-            stat.copy_(torch.where(inside, torch.minimum(stat, x), stat))
-        else:
-            stat.copy_(torch.where(inside, torch.maximum(stat, x), stat))
-        count += inside.to(count.dtype)
-
-    @staticmethod
-    def ensemble_finalize_masked(stat, count, out, mode):
-        from pytorch_connectomics_amd.inference.tta import _MODE_CODE
-        out.copy_(stat / count if mode == _MODE_CODE["mean"] else stat)
+from window_kernel_model import KernelModel as _Ops      # the shared CPU model of the window kernels
 
 
 def _net_lazy(x):
