@@ -132,18 +132,6 @@ __global__ void __launch_bounds__(CLD_THREADS) cldice_erode_kernel(const float* 
   dst[t] = erode_at(src, t, z, y, x, g, m, o);
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = CLD_THREADS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // skeleton s_n of every voxel (written when skel is non-null) and, when other is non-null, the tile partials
 //   partial[(vol tiles + tile) 2 + 0] = sum (s w)(other w),   [.. + 1] = sum s w        (w = 1 when weight is null)
 __global__ void __launch_bounds__(CLD_THREADS) cldice_skeleton_kernel(const float* __restrict__ p0, const float* __restrict__ P,
@@ -180,8 +168,8 @@ __global__ void __launch_bounds__(CLD_THREADS) cldice_skeleton_kernel(const floa
     }
   }
   if (!other) return;
-  acc0 = block_sum(acc0, red);
-  acc1 = block_sum(acc1, red);
+  acc0 = block_sum<CLD_THREADS>(acc0, red);
+  acc1 = block_sum<CLD_THREADS>(acc1, red);
   if (threadIdx.x == 0) {
     partial[((long)vol * tiles + tile) * 2 + 0] = acc0;
     partial[((long)vol * tiles + tile) * 2 + 1] = acc1;
@@ -197,8 +185,8 @@ __global__ void __launch_bounds__(CLD_THREADS) cldice_sum_kernel(const float* __
     a0 += partial[((long)vol * tiles + t) * 2 + 0];
     a1 += partial[((long)vol * tiles + t) * 2 + 1];
   }
-  a0 = block_sum(a0, red);
-  a1 = block_sum(a1, red);
+  a0 = block_sum<CLD_THREADS>(a0, red);
+  a1 = block_sum<CLD_THREADS>(a1, red);
   if (threadIdx.x == 0) {
     sums[vol * 2 + 0] = a0;
     sums[vol * 2 + 1] = a1;

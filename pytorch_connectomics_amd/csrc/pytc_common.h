@@ -138,6 +138,22 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// ---- workgroup reduction ------------------------------------------------------------------
+// The sum of v over a workgroup of THREADS threads, returned to every thread: an LDS halving tree over red[THREADS] in a fixed
+// order (bit-reproducible).  The closing barrier leaves red free for the next call.
+template <int THREADS, typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const T r = red[0];
+  __syncthreads();
+  return r;
+}
+
 // erf GELU (torch.nn.functional.gelu(approximate='none')) with erf from Abramowitz-Stegun 7.1.26
 // (|abs err| <= 1.5e-7), evaluated as 1+erf(z) = p(t)exp(-z^2) for z<0 and 2 - p(t)exp(-z^2) for
 // z>0 so the negative tail has no cancellation.  ~14 VALU + v_rcp_f32 + v_exp_f32, branch free.

@@ -39,18 +39,6 @@ struct RgGeo {
   int flag;
 };
 
-__device__ __forceinline__ float rg_block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = RG_THREADS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // s = sigmoid(x), sc = sigmoid(-x), both without cancellation
 __device__ __forceinline__ void rg_sig2(float x, float& s, float& sc) {
   const float e = expf(-fabsf(x));
@@ -180,7 +168,7 @@ __global__ void __launch_bounds__(RG_THREADS) reg_forward_kernel(const float* __
       if (i < g.V) s += rg_loss<KIND>(pa[i], pb ? pb[i] : 0.f, pc ? pc[i] : 0.f, pc != nullptr, g) * (pm ? pm[i] : 1.f);
     }
   }
-  s = rg_block_sum(s, red);
+  s = block_sum<RG_THREADS>(s, red);
   if (threadIdx.x == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
@@ -189,7 +177,7 @@ __global__ void __launch_bounds__(RG_THREADS) reg_sum_kernel(const float* __rest
   __shared__ float red[RG_THREADS];
   float s = 0.f;
   for (long i = threadIdx.x; i < n; i += RG_THREADS) s += partial[i];
-  s = rg_block_sum(s, red);
+  s = block_sum<RG_THREADS>(s, red);
   if (threadIdx.x == 0) sum[0] = s;
 }
 
@@ -358,7 +346,7 @@ __global__ void __launch_bounds__(FC_THREADS) fgcontour_forward_kernel(const flo
       s += (d * d) * (mask ? mask[i] : 1.f);
     }
   }
-  s = rg_block_sum(s, red);
+  s = block_sum<FC_THREADS>(s, red);
   if (threadIdx.x == 0) partial[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 

@@ -66,30 +66,6 @@ __device__ __forceinline__ void sc_tile_origin(int tile, const ScGeo& g, int& z0
   z0 = (rem / g.ny) * g.tz;
 }
 
-__device__ __forceinline__ float sc_block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = SC_THREADS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
-__device__ __forceinline__ int sc_block_sum(int v, int* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = SC_THREADS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const int r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // the two staged values of one voxel
 __device__ __forceinline__ void sc_gate(float x, float t, float& a, float& b) {
   const bool fg = t > 0.5f;
@@ -205,12 +181,12 @@ __global__ void __launch_bounds__(SC_THREADS) scnp_forward_kernel(const float* _
     __syncthreads();
   }
   if (!partial) return;
-  s0 = sc_block_sum(s0, red);
-  s1 = sc_block_sum(s1, red);
+  s0 = block_sum<SC_THREADS>(s0, red);
+  s1 = block_sum<SC_THREADS>(s1, red);
   int* redi = reinterpret_cast<int*>(red);
-  n0 = sc_block_sum(n0, redi);
-  n1 = sc_block_sum(n1, redi);
-  n2 = sc_block_sum(n2, redi);
+  n0 = block_sum<SC_THREADS>(n0, redi);
+  n1 = block_sum<SC_THREADS>(n1, redi);
+  n2 = block_sum<SC_THREADS>(n2, redi);
   if (threadIdx.x == 0) {
     float* p = partial + ((long)vol * gridDim.x + blockIdx.x) * SC_TERMS;
     p[0] = s0;
@@ -235,12 +211,12 @@ __global__ void __launch_bounds__(SC_THREADS) scnp_sum_kernel(const float* __res
     c1 += __float_as_int(p[3]);
     c2 += __float_as_int(p[4]);
   }
-  a0 = sc_block_sum(a0, red);
-  a1 = sc_block_sum(a1, red);
+  a0 = block_sum<SC_THREADS>(a0, red);
+  a1 = block_sum<SC_THREADS>(a1, red);
   int* redi = reinterpret_cast<int*>(red);
-  c0 = sc_block_sum(c0, redi);
-  c1 = sc_block_sum(c1, redi);
-  c2 = sc_block_sum(c2, redi);
+  c0 = block_sum<SC_THREADS>(c0, redi);
+  c1 = block_sum<SC_THREADS>(c1, redi);
+  c2 = block_sum<SC_THREADS>(c2, redi);
   if (threadIdx.x == 0) {
     float* o = sums + (long)vol * SC_TERMS;
     o[0] = a0;

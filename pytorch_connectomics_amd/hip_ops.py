@@ -2282,19 +2282,48 @@ def deconv2_upfirst_bwd(dout: torch.Tensor, x_low: torch.Tensor, weight: torch.T
     return dx_e, dx_low, dW, db
 
 
+# ---- the loss kernels' operand checks: each loss words its own errors around these three -----------------------------------------
+def _volume_geo(x: torch.Tensor):
+    """(N, C, D, H, W, is2d) of a (N, C, D, H, W) or (N, C, H, W) volume; None for any other rank."""
+    if x.dim() == 5:
+        N, C_, D, H, W = (int(v) for v in x.shape)
+        return N, C_, D, H, W, 0
+    if x.dim() == 4:
+        N, C_, H, W = (int(v) for v in x.shape)
+        return N, C_, 1, H, W, 1
+    return None
+
+
+def _channels_or_one(t: torch.Tensor, like: torch.Tensor, name: str, contiguous: bool = True) -> int:
+    """The channel count of a weight or mask for the operand `like` (N, C, ...): fp32 with like's batch and spatial dims and C channels
+    or one."""
+    if contiguous:
+        _dev(t, name)
+    wC = int(t.shape[1]) if t.dim() == like.dim() else -1
+    if t.dtype != torch.float32 or wC not in (1, int(like.shape[1])) or t.shape[0] != like.shape[0] or t.shape[2:] != like.shape[2:]:
+        raise ValueError(f"{name} must be float32 of shape {tuple(like.shape)} or with one channel, got {t.dtype} {tuple(t.shape)}")
+    return wC
+
+
+def _device_floats(t: torch.Tensor, name: str, n: Optional[int] = None, what: str = "") -> torch.Tensor:
+    """A coefficient tensor as the kernels read it: contiguous fp32 on the device, `n` values (`what` names the count in the error)."""
+    t = _dev(t.to(torch.float32).reshape(-1).contiguous(), name)
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{name} must hold {what}, got {t.numel()}")
+    return t
+
+
 # ---- clDice soft skeleton (csrc/cldice_kernels.hip) -----------------------------------------------------------------------------
 def _cldice_geo(x: torch.Tensor, name: str):
     """(nvol, D, H, W, is2d) of a contiguous fp32 (N, C, D, H, W) or (N, C, H, W) volume."""
     _dev(x, name)
     if x.dtype != torch.float32:
         raise TypeError(f"{name}: the clDice kernels take float32, got {x.dtype}")
-    if x.dim() == 5:
-        N, C_, D, H, W = (int(v) for v in x.shape)
-        return N * C_, D, H, W, 0
-    if x.dim() == 4:
-        N, C_, H, W = (int(v) for v in x.shape)
-        return N * C_, 1, H, W, 1
-    raise ValueError(f"{name}: expected a 4-D or 5-D tensor, got shape {tuple(x.shape)}")
+    geo = _volume_geo(x)
+    if geo is None:
+        raise ValueError(f"{name}: expected a 4-D or 5-D tensor, got shape {tuple(x.shape)}")
+    N, C_, D, H, W, is2d = geo
+    return N * C_, D, H, W, is2d
 
 
 def cldice_levels(prob: torch.Tensor, num_iters: int) -> torch.Tensor:
@@ -2345,9 +2374,7 @@ def cldice_backward(prob: torch.Tensor, P: torch.Tensor, num_iters: int, target:
     n = int(num_iters)
     _dev(P, "P")
     _dev(target, "target")
-    coef = _dev(coef.to(torch.float32).contiguous(), "coef")
-    if coef.numel() != 3 * nvol:
-        raise ValueError(f"coef must hold 3 x {nvol} values, got {coef.numel()}")
+    coef = _device_floats(coef, "coef", 3 * nvol, f"3 x {nvol} values")
     gdiff = torch.empty((n + 1, *prob.shape), dtype=torch.float32, device=prob.device)
     arg = torch.empty((n + 1, *prob.shape), dtype=torch.uint8, device=prob.device)
     lib = nat.lib()
@@ -2377,20 +2404,11 @@ def _scnp_geo(x: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor], ns: i
     _dev(t, "target")
     if x.dtype != torch.float32 or t.dtype != torch.float32 or t.shape != x.shape:
         raise ValueError(f"logits and target must be float32 of one shape, got {x.dtype} {tuple(x.shape)} and {t.dtype} {tuple(t.shape)}")
-    if x.dim() == 5:
-        N, C_, D, H, W = (int(v) for v in x.shape)
-        is2d = 0
-    elif x.dim() == 4:
-        N, C_, H, W = (int(v) for v in x.shape)
-        D, is2d = 1, 1
-    else:
+    geo = _volume_geo(x)
+    if geo is None:
         raise ValueError(f"ScnpLoss expects 4D [B,C,H,W] or 5D [B,C,Z,Y,X] logits, got {x.dim()}D.")
-    wC = C_
-    if w is not None:
-        _dev(w, "weight")
-        wC = int(w.shape[1]) if w.dim() == x.dim() else -1
-        if w.dtype != torch.float32 or wC not in (1, C_) or w.shape[0] != x.shape[0] or w.shape[2:] != x.shape[2:]:
-            raise ValueError(f"weight must be float32 of shape {tuple(x.shape)} or with one channel, got {w.dtype} {tuple(w.shape)}")
+    N, C_, D, H, W, is2d = geo
+    wC = C_ if w is None else _channels_or_one(w, x, "weight")
     return N, C_, wC, D, H, W, is2d
 
 
@@ -2422,8 +2440,7 @@ def scnp_backward(x: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor], a
     _dev(arg, "arg")
     if arg.shape != x.shape or arg.dtype != (torch.uint8 if int(ns) <= 5 else torch.int16):
         raise ValueError(f"arg must be the code map scnp_forward wrote for neighborhood_size={int(ns)}, got {arg.dtype} {tuple(arg.shape)}")
-    coef = _dev(coef.to(torch.float32).contiguous(), "coef")
-    pos_weight = _dev(pos_weight.to(torch.float32).contiguous(), "pos_weight")
+    coef, pos_weight = _device_floats(coef, "coef"), _device_floats(pos_weight, "pos_weight")
     if coef.numel() != N * C_ or pos_weight.numel() != N * C_:
         raise ValueError(f"coef and pos_weight must hold {N} x {C_} values, got {coef.numel()} and {pos_weight.numel()}")
     dx = torch.empty_like(x)
@@ -2469,10 +2486,7 @@ def _reg_geo(kind: str, a: torch.Tensor, b: Optional[torch.Tensor], mask: Option
         if mask is not None:
             raise ValueError("NonOverlapRegularization takes no mask")
     elif mask is not None:
-        _dev(mask, "mask")
-        wC = int(mask.shape[1]) if mask.dim() == a.dim() else -1
-        if mask.dtype != torch.float32 or wC not in (1, C_) or mask.shape[0] != a.shape[0] or mask.shape[2:] != a.shape[2:]:
-            raise ValueError(f"mask must be float32 of shape {tuple(a.shape)} or with one channel, got {mask.dtype} {tuple(mask.shape)}")
+        wC = _channels_or_one(mask, a, "mask")
     return REG_KINDS[kind], N, C_, wC, V
 
 
@@ -2494,9 +2508,7 @@ def reg_pointwise_backward(kind: str, coef: torch.Tensor, a: torch.Tensor, b: Op
     """-> (da, db): coef x mask x the gradient of the loss in each operand (db None for the one-operand kinds); coef is one device
     float.  For 'nonoverlap' da is the gradient of the whole (N, C, ...) tensor, zero outside channels 0 and 1."""
     k, N, C_, wC, V = _reg_geo(kind, a, b, mask)
-    coef = _dev(coef.to(torch.float32).reshape(-1).contiguous(), "coef")
-    if coef.numel() != 1:
-        raise ValueError(f"coef must hold one value, got {coef.numel()}")
+    coef = _device_floats(coef, "coef", 1, "one value")
     da = torch.empty_like(a)
     db = torch.empty_like(b) if b is not None else None
     _run(f"reg_pointwise_backward[{kind}]", _nbytes(a, b, mask, da, db), nat.lib().pytc_reg_pointwise_backward, k, _p(a), _p(b), _p(mask),
@@ -2520,7 +2532,7 @@ def _fgcontour_geo(fg: torch.Tensor, contour: torch.Tensor, mask: Optional[torch
             raise ValueError(f"mask must be float32 of shape {tuple(fg.shape)}, got {mask.dtype} {tuple(mask.shape)}")
     if not 0.0 < float(eps) < 0.5:
         raise ValueError(f"eps must lie in (0, 0.5) for the HIP kernels, got {eps}")
-    N, _, D, H, W = (int(v) for v in fg.shape)
+    N, _, D, H, W, _ = _volume_geo(fg)
     return N, D, H, W
 
 
@@ -2544,9 +2556,7 @@ def fgcontour_backward(coef: torch.Tensor, fg: torch.Tensor, contour: torch.Tens
     _dev(code, "code")
     if code.shape != fg.shape or code.dtype != torch.uint8:
         raise ValueError(f"code must be the uint8 map fgcontour_forward wrote, got {code.dtype} {tuple(code.shape)}")
-    coef = _dev(coef.to(torch.float32).reshape(-1).contiguous(), "coef")
-    if coef.numel() != 1:
-        raise ValueError(f"coef must hold one value, got {coef.numel()}")
+    coef = _device_floats(coef, "coef", 1, "one value")
     dfg, dct = torch.empty_like(fg), torch.empty_like(contour)
     _run("fgcontour_backward", _nbytes(fg, contour, mask, code, dfg, dct), nat.lib().pytc_fgcontour_backward, _p(fg), _p(contour),
          _p(mask), _p(code), _p(coef), _p(dfg), _p(dct), N, D, H, W, float(eps), _stream())
@@ -2605,11 +2615,9 @@ def _softmax_loss_operands(x: torch.Tensor, target: torch.Tensor, mask: Optional
     x, xs = _strided(x)
     m, ms = None, None
     if mask is not None:
-        if mask.dtype != torch.float32 or mask.dim() != x.dim() or mask.shape[0] != N or mask.shape[1] not in (1, C_) \
-                or mask.shape[2:] != x.shape[2:]:
-            raise ValueError(f"mask must be float32 of shape {tuple(x.shape)} or with one channel, got {mask.dtype} {tuple(mask.shape)}")
+        wC = _channels_or_one(mask, x, "mask", contiguous=False)             # in any layout: the kernels take its strides
         m, ms = _strided(mask)
-        if mask.shape[1] == 1:
+        if wC == 1:
             ms[1] = 0
     return x, xs, t, ts, m, ms, kind, N, C_, R
 

@@ -16,6 +16,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .hip_dispatch import wants_hip
+
 
 # ---- restatement of the reference's soft morphology (losses.py:47-85) -------------------------------------------------------------
 def _soft_erode_pool(prob: torch.Tensor) -> torch.Tensor:
@@ -211,9 +213,7 @@ class SoftClDiceLoss(nn.Module):
     def forward(self, pred: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         if pred.ndim not in {4, 5}:
             raise ValueError(f"SoftClDiceLoss expects 4D/5D tensors, got {tuple(pred.shape)}")
-        hip = pred.is_cuda if self.use_hip is None else bool(self.use_hip)
-        if hip and not pred.is_cuda:
-            raise RuntimeError("SoftClDiceLoss(use_hip=True) needs CUDA(HIP) tensors: the HIP kernels have no CPU path")
+        hip = wants_hip(self.use_hip, pred, "SoftClDiceLoss")
 
         pred = self._apply_activation(pred)
         target, class_index = self._check_target_shape(target, pred)
@@ -278,13 +278,3 @@ class SoftClDiceLoss(nn.Module):
             return loss.sum()
         return loss.mean()
 
-
-def soft_cldice_term(pred, target, weight=None, **kwargs):
-    """The `SoftClDiceLoss` term of ConnectomicsModule: the loss with the term's kwargs and the spatial weight the orchestrator hands
-    it.  `reduction: none` leaves a per-(sample, channel) tensor, which the reference's orchestrator cannot take as a term unless it
-    holds one value (its finiteness check and `.item()` fail otherwise); the same case is refused here by name."""
-    v = SoftClDiceLoss(**kwargs)(pred, target, weight=weight)
-    if v.numel() != 1:
-        raise ValueError(f"SoftClDiceLoss with reduction='none' returned a loss of shape {tuple(v.shape)}: a training loss term must "
-                         "reduce to one value (use reduction 'mean' or 'sum')")
-    return v

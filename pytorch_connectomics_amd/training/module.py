@@ -21,244 +21,14 @@ import torch.nn.functional as F
 from ..models import build_model
 from ..utils.channel_slices import resolve_channel_indices
 from ..utils.model_outputs import resolve_head_target_slice, unwrap_main_output
-from .cldice_autograd import SoftClDiceLoss, soft_cldice_term
-from .regularization_autograd import REGULARIZATION_LOSSES
-from .scnp_autograd import ScnpLoss, scnp_term
-from .softmax_loss_autograd import SOFTMAX_LOSSES, check_softmax_dice_kwargs, softmax_dice_loss
+from .loss_table import loss_row
+from .losses import (_mask_for_unweighted_loss, auto_pos_weight_scalar, class_balance_weight,  # noqa: F401  (re-exported: callers
+                     dice_loss_sigmoid, monai_dice_loss, monai_focal_loss, monai_tversky_loss,     # and the exact-epilogue tests read
+                     per_channel_bce_with_logits, weighted_bce_with_logits, weighted_regression_loss)   # them from this module)
 
 _NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d,
                nn.InstanceNorm2d, nn.InstanceNorm3d, nn.LayerNorm, nn.LocalResponseNorm)
 DS_WEIGHTS = [1.0, 0.5, 0.25, 0.125, 0.0625]
-
-
-def dice_loss_sigmoid(logits: torch.Tensor, target: torch.Tensor, smooth_nr: float = 1e-5, smooth_dr: float = 1e-5):
-    """MONAI DiceLoss(sigmoid=True) semantics: per (B, C) dice over spatial dims, mean over B and C."""
-    p = torch.sigmoid(logits.float())
-    t = target.float()
-    dims = tuple(range(2, p.dim()))
-    inter = (p * t).sum(dims)
-    den = p.sum(dims) + t.sum(dims)
-    return (1.0 - (2.0 * inter + smooth_nr) / (den + smooth_dr)).mean()
-
-
-def _mask_for_unweighted_loss(pred, target, mask, clamp_min: float):
-    """Losses without a spatial-weight argument (the MONAI ones) see a mask through their INPUTS
-    (training/losses/orchestrator.py:648-655): invalid voxels get the clamp floor as logit and 0 as target."""
-    if mask is None:
-        return pred, target
-    valid = (mask > 0).expand_as(pred)
-    return pred.masked_fill(~valid, float(clamp_min)), target * (mask > 0).to(target.dtype)
-
-
-def _drop_background(p, t, include_background: bool):
-    if include_background or p.shape[1] == 1:          # MONAI: "single channel prediction, include_background=False ignored"
-        return p, t
-    return p[:, 1:], t[:, 1:]
-
-
-def monai_dice_loss(logits, target, *, sigmoid: bool = False, include_background: bool = True, smooth_nr=1e-5, smooth_dr=1e-5,
-                    squared_pred: bool = False, **_unused):
-    """monai.losses.DiceLoss as the reference instantiates it (models/losses/build.py:58-61; reduction 'mean', batch=False):
-    1 - (2 sum(p t) + smooth_nr) / (sum(p) + sum(t) + smooth_dr) per (B, C) over the spatial dims, mean over B and C.
-    `sigmoid` defaults to False as in MONAI (a config that omits it trains Dice on the raw logits).  Parity unpinned: MONAI
-    is not in the image; restated from its documented formula."""
-    p = torch.sigmoid(logits.float()) if sigmoid else logits.float()
-    t = target.float()
-    p, t = _drop_background(p, t, bool(include_background))
-    dims = tuple(range(2, p.dim()))
-    inter = (p * t).sum(dims)
-    den = ((p * p).sum(dims) + (t * t).sum(dims)) if squared_pred else (p.sum(dims) + t.sum(dims))
-    return (1.0 - (2.0 * inter + float(smooth_nr)) / (den + float(smooth_dr))).mean()
-
-
-def monai_tversky_loss(logits, target, *, sigmoid: bool = False, include_background: bool = True, alpha: float = 0.5,
-                       beta: float = 0.5, smooth_nr=1e-5, smooth_dr=1e-5, **_unused):
-    """monai.losses.TverskyLoss: tp = sum(p t), fp = alpha sum(p (1 - t)), fn = beta sum((1 - p) t) per (B, C);
-    1 - (tp + smooth_nr) / (tp + fp + fn + smooth_dr), mean.  Parity unpinned (see monai_dice_loss)."""
-    p = torch.sigmoid(logits.float()) if sigmoid else logits.float()
-    t = target.float()
-    p, t = _drop_background(p, t, bool(include_background))
-    dims = tuple(range(2, p.dim()))
-    tp = (p * t).sum(dims)
-    fp = float(alpha) * (p * (1.0 - t)).sum(dims)
-    fn = float(beta) * ((1.0 - p) * t).sum(dims)
-    return (1.0 - (tp + float(smooth_nr)) / (tp + fp + fn + float(smooth_dr))).mean()
-
-
-def monai_focal_loss(logits, target, *, gamma: float = 2.0, alpha=None, include_background: bool = True, **_unused):
-    """monai.losses.FocalLoss (sigmoid form, use_softmax=False, reduction 'mean'): BCE-with-logits * (1 - p_t)^gamma, with
-    alpha: * (alpha t + (1 - alpha)(1 - t)); mean over every element.  Parity unpinned (see monai_dice_loss)."""
-    x, t = logits.float(), target.float()
-    x, t = _drop_background(x, t, bool(include_background))
-    bce = F.binary_cross_entropy_with_logits(x, t, reduction="none")
-    # (1 - p_t)^gamma = exp(gamma * logsigmoid(-x (2t - 1))): stable for large |x|
-    mod = torch.exp(float(gamma) * F.logsigmoid(-x * (2.0 * t - 1.0)))
-    loss = mod * bce
-    if alpha is not None:
-        loss = loss * (float(alpha) * t + (1.0 - float(alpha)) * (1.0 - t))
-    return loss.mean()
-
-
-def auto_pos_weight_scalar(target, mask=None, cap: float = 10.0) -> torch.Tensor:
-    """`pos_weight: auto` of a weighted-BCE term (orchestrator.py:180-197): min(neg / pos, 10) over the valid voxels, 1 when
-    either class is absent -- computed on the device, no host synchronisation."""
-    valid = torch.ones_like(target, dtype=torch.bool) if mask is None else (mask > 0).expand_as(target)
-    pos = ((target > 0) & valid).sum().float()
-    neg = ((target <= 0) & valid).sum().float()
-    ratio = torch.clamp(neg / pos.clamp_min(1.0), max=float(cap))
-    return torch.where((pos > 0) & (neg > 0), ratio, torch.ones_like(ratio)).reshape(1)
-
-
-def class_balance_weight(target: torch.Tensor, pos_weight=None, valid_mask=None, cap: float = 10.0) -> torch.Tensor:
-    """The spatial weight map the reference's orchestrator hands to every `weight`-taking loss except the weighted BCE when a term
-    carries no mask of its own (orchestrator.py:129-178, :606-612).  `pos_weight` None / "auto": foreground (target > 0) and
-    background weights in the ratio neg : pos, scaled so that the valid voxels average 1, each capped at `cap`; ones when a class
-    is absent.  A number: that weight on the foreground, 1 elsewhere.  Counts stay on the device (no host synchronisation)."""
-    t = target
-    ones = torch.ones_like(t)
-    if pos_weight is not None and not isinstance(pos_weight, str):
-        fg = float(pos_weight)
-        if fg <= 0:
-            raise ValueError(f"pos_weight must be > 0, got {fg}")
-        return torch.where(t > 0, ones * fg, ones)
-    if isinstance(pos_weight, str) and pos_weight != "auto":
-        raise ValueError(f"Unsupported pos_weight mode: {pos_weight!r}. Expected a positive number or 'auto'.")
-    valid = torch.ones_like(t, dtype=torch.bool) if valid_mask is None else (valid_mask > 0).expand_as(t)
-    pos = ((t > 0) & valid).sum().to(t.dtype if t.is_floating_point() else torch.float32)
-    neg = ((t <= 0) & valid).sum().to(pos.dtype)
-    both = (pos > 0) & (neg > 0)
-    count = pos + neg
-    fg = torch.clamp(count / (2.0 * pos.clamp_min(1.0)), max=float(cap))
-    bg = torch.clamp(count / (2.0 * neg.clamp_min(1.0)), max=float(cap))
-    balanced = torch.where(t > 0, ones * fg, ones * bg)
-    return torch.where(both, balanced, ones)
-
-
-# losses whose spatial argument is a WEIGHT map (reference models/losses/metadata.py:38-48); every other loss sees a mask as
-# "logits at the clamp minimum, target 0" outside it
-_WEIGHT_TAKING = {"SmoothL1Loss", "WeightedBCEWithLogitsLoss", "PerChannelBCEWithLogitsLoss", "WeightedMSELoss", "WeightedMAELoss",
-                  "SoftClDiceLoss", "ScnpLoss"}
-_OWN_CLASS_BALANCE = {"WeightedBCEWithLogitsLoss", "PerChannelBCEWithLogitsLoss"}      # pos_weight defaults to 1 there (plan.py:105-112)
-
-
-def per_channel_bce_with_logits(logits, target, weight=None, *, auto_pos_weight: bool = True, max_pos_weight: float = 10.0,
-                                reduction: str = "mean"):
-    """models/losses/losses.py:269-351: BCE per channel with its own class-balancing weight min(n_neg / n_pos, max_pos_weight)
-    (1 for a channel without positives) from the valid voxels of the current batch, reduced per channel (weighted-valid mean or
-    sum), summed over the channels."""
-    x, t = logits.float(), target.float()
-    C = x.shape[1]
-    pw = None
-    if auto_pos_weight:
-        valid = (weight > 0).expand_as(t) if weight is not None else torch.ones_like(t, dtype=torch.bool)
-        dims = (0,) + tuple(range(2, t.dim()))
-        pos = ((t > 0) & valid).sum(dims).float()
-        neg = ((t <= 0) & valid).sum(dims).float()
-        ratio = torch.clamp(neg / pos.clamp_min(1.0), max=float(max_pos_weight))
-        pw = torch.where(pos > 0, ratio, torch.ones_like(ratio)).reshape(1, C, *([1] * (t.dim() - 2)))
-    bce = F.binary_cross_entropy_with_logits(x, t, pos_weight=pw, reduction="none")
-    total = x.new_zeros(())
-    w = None if weight is None else weight.float().expand_as(bce)
-    for c in range(C):
-        b = bce[:, c:c + 1]
-        if w is None:
-            total = total + (b.mean() if reduction == "mean" else b.sum())
-        else:
-            wc = w[:, c:c + 1]
-            bw = b * wc
-            valid_c = wc > 0
-            total = total + ((bw * valid_c).sum() / valid_c.sum().clamp_min(1) if reduction == "mean" else bw.sum())
-    return total
-
-
-def weighted_bce_with_logits(logits, target, weight=None, pos_weight=None):
-    """models/losses/losses.py:17-44,190-266 (reduction='mean'; with a weight map: the mean of weight * bce over the
-    voxels whose weight is > 0, the map broadcast to the logits' shape; 0 when no voxel is valid)."""
-    if pos_weight is None:
-        pw = None
-    elif isinstance(pos_weight, str):
-        if pos_weight != "auto":
-            raise ValueError(f"Unsupported pos_weight mode: {pos_weight!r}. Expected a positive number or 'auto'.")
-        pw = auto_pos_weight_scalar(target, weight).to(logits.device)
-    elif isinstance(pos_weight, torch.Tensor):
-        pw = pos_weight.to(device=logits.device, dtype=torch.float32)
-    else:
-        if float(pos_weight) <= 0:
-            raise ValueError(f"pos_weight must be > 0, got {float(pos_weight)}")
-        pw = torch.as_tensor([float(pos_weight)], device=logits.device, dtype=torch.float32)
-    bce = F.binary_cross_entropy_with_logits(logits.float(), target.float(), pos_weight=pw, reduction="none")
-    if weight is None:
-        return bce.mean()
-    w = weight.float().expand_as(bce)
-    valid = w > 0
-    return (bce * w * valid).sum() / valid.sum().clamp_min(1)
-
-
-def _reduce_weighted(loss: torch.Tensor, weight: Optional[torch.Tensor]) -> torch.Tensor:
-    """losses.py:17-44 with reduction='mean': plain mean, or the mean of weight * loss over the voxels with weight > 0."""
-    if weight is None:
-        return loss.mean()
-    w = weight.float().expand_as(loss)
-    valid = w > 0
-    return (loss * w * valid).sum() / valid.sum().clamp_min(1)
-
-
-def weighted_regression_loss(kind: str, pred, target, weight=None, *, tanh: bool = False, beta: float = 1.0):
-    """WeightedMSELoss / WeightedMAELoss / SmoothL1Loss of the reference (losses.py:140-187, 725-800): optional tanh on
-    the prediction (distance-transform targets in [-1, 1]), elementwise loss, weighted-valid mean."""
-    p = pred.float()
-    if tanh:
-        p = torch.tanh(p)
-    t = target.float()
-    if kind == "mse":
-        loss = (p - t) ** 2
-    elif kind == "mae":
-        loss = (p - t).abs()
-    else:
-        loss = F.smooth_l1_loss(p, t, beta=float(beta), reduction="none")
-    return _reduce_weighted(loss, weight)
-
-
-_LOSSES = {
-    "WeightedMSELoss": lambda p, t, **kw: weighted_regression_loss("mse", p, t, kw.get("weight"), tanh=bool(kw.get("tanh", False))),
-    "WeightedMAELoss": lambda p, t, **kw: weighted_regression_loss("mae", p, t, kw.get("weight"), tanh=bool(kw.get("tanh", False))),
-    "SmoothL1Loss": lambda p, t, **kw: weighted_regression_loss("huber", p, t, kw.get("weight"), tanh=bool(kw.get("tanh", False)),
-                                                                beta=float(kw.get("beta", 1.0))),
-    "DiceLoss": lambda p, t, **kw: monai_dice_loss(*_mask_for_unweighted_loss(p, t, kw.get("weight"), kw.get("clamp_min", -20.0)),
-                                                   **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
-    "TverskyLoss": lambda p, t, **kw: monai_tversky_loss(*_mask_for_unweighted_loss(p, t, kw.get("weight"), kw.get("clamp_min", -20.0)),
-                                                         **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
-    "FocalLoss": lambda p, t, **kw: monai_focal_loss(*_mask_for_unweighted_loss(p, t, kw.get("weight"), kw.get("clamp_min", -20.0)),
-                                                     **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
-    "PerChannelBCEWithLogitsLoss": lambda p, t, **kw: per_channel_bce_with_logits(
-        p, t, kw.get("weight"), auto_pos_weight=bool(kw.get("auto_pos_weight", True)),
-        max_pos_weight=float(kw.get("max_pos_weight", 10.0)), reduction=str(kw.get("reduction", "mean"))),
-    "WeightedBCEWithLogitsLoss": lambda p, t, **kw: weighted_bce_with_logits(p, t, kw.get("weight"), kw.get("pos_weight")),
-    # torch's own losses take no spatial argument: a mask reaches them as "logit at the clamp minimum, target 0" outside it
-    "BCEWithLogitsLoss": lambda p, t, **kw: F.binary_cross_entropy_with_logits(
-        *(v.float() for v in _mask_for_unweighted_loss(p, t, kw.get("weight"), kw.get("clamp_min", -20.0)))),
-    "MSELoss": lambda p, t, **kw: F.mse_loss(*(v.float() for v in _mask_for_unweighted_loss(p, t, kw.get("weight"), kw.get("clamp_min", -20.0)))),
-    # topology loss (losses.py:456-721): soft skeletons on HIP for CUDA tensors (training/cldice_autograd.py)
-    "SoftClDiceLoss": lambda p, t, **kw: soft_cldice_term(p, t, kw.get("weight"),
-                                                          **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
-    # neighbour-penalised per-channel BCE (losses.py:354-453): pooled logits, sums and gradient on HIP (training/scnp_autograd.py)
-    "ScnpLoss": lambda p, t, **kw: scnp_term(p, t, kw.get("weight"),
-                                             **{k: v for k, v in kw.items() if k not in ("weight", "pos_weight", "clamp_min")}),
-}
-# the regularisers (models/losses/regularization.py; value and gradients on HIP, training/regularization_autograd.py) take no target:
-# a `pred_only` loss is called on one prediction slice, a `pred_pred` loss on two, and those with a `mask` argument get the term's
-# combined mask (models/losses/metadata.py:53-76).  A term holds its loss instance, built once with the module.
-_LOSSES.update({name: cls for name, (cls, _kind, _arg) in REGULARIZATION_LOSSES.items()})
-_CALL_KINDS = {name: (kind, arg) for name, (_cls, kind, arg) in REGULARIZATION_LOSSES.items()}     # every other loss: pred_target
-# the softmax losses and L1Loss (training/softmax_loss_autograd.py): no spatial weight argument; the term's mask reaches them -- and,
-# for the softmax ones, the HIP kernels -- as `mask` with fill = the clamp minimum, never as a masked_fill copy of the logits
-_LOSSES.update({name: fn for name, (fn, _check, _kind) in SOFTMAX_LOSSES.items()})            # called as fn(pred, target, mask, fill=, **kwargs)
-_TARGET_KINDS = {name: kind for name, (_fn, _check, kind) in SOFTMAX_LOSSES.items()}                # every other loss: dense
-
-
-def _is_softmax_dice(fn: str, kwargs) -> bool:
-    """A DiceLoss term takes the softmax path only when `softmax` or `to_onehot_y` is set; the sigmoid / plain form keeps its own."""
-    return fn == "DiceLoss" and bool(kwargs.get("softmax", False) or kwargs.get("to_onehot_y", False))
 
 
 def match_target_to_output(target: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
@@ -413,6 +183,70 @@ def build_lr_scheduler(cfg, optimizer):
                                 eta_min=float(_sched_param(sc, "min_lr", 1e-6)))
 
 
+_DEFAULT_TERMS = [{"function": "WeightedBCEWithLogitsLoss", "weight": 1.0},
+                  {"function": "DiceLoss", "weight": 1.0, "kwargs": {"sigmoid": True}}]
+
+
+def plan_loss_terms(cfg) -> list:
+    """model.loss.losses -> the term mappings `_term_loss` works from (training/losses/plan.py:126-237), every check of a term run
+    here, when the module is built.  A term's loss is built once (`loss`), from its row of training/loss_table.py (`row`)."""
+    terms = getattr(getattr(cfg.model, "loss", None), "losses", None) or _DEFAULT_TERMS
+    heads = getattr(cfg.model, "heads", None)
+    heads = heads if isinstance(heads, Mapping) else {}
+    primary = getattr(cfg.model, "primary_head", None)
+    plan = []
+    for n, t in enumerate(terms):
+        get = t.get if isinstance(t, dict) else (lambda k, d=None, _t=t: getattr(_t, k, d))
+        where = f"losses[{n}]"
+        fn, kwargs = get("function"), dict(get("kwargs", None) or {})
+        row = loss_row(fn, kwargs)
+        loss = row.build(**kwargs)                 # the loss's argument checks run when the module is built, as in the reference
+        # how the loss is called (training/losses/plan.py:158-237): the kind is the loss's own; a term may restate it
+        call_kind = str(get("call_kind", get("call", row.call)))
+        if call_kind != row.call:
+            raise ValueError(f"Unsupported call_kind {call_kind!r} in {where}")
+        pos_weight = get("pos_weight")
+        if isinstance(pos_weight, str):
+            if pos_weight.strip().lower() != "auto":
+                raise ValueError(f"{where} pos_weight must be a positive number or 'auto', got {pos_weight!r}")
+            pos_weight = "auto"
+        elif pos_weight is not None and float(pos_weight) <= 0:
+            raise ValueError(f"{where} pos_weight must be > 0, got {float(pos_weight)}")
+        # which head a term reads is settled when the module is built (training/losses/plan.py:183-229): pred_head, else
+        # model.primary_head, else the only head; a term that names no target channels takes that head's `target_slice`
+        pred_head, pred2_head = get("pred_head"), get("pred2_head")
+        if heads:
+            if pred_head is not None and pred_head not in heads:
+                raise ValueError(f"{where} pred_head={pred_head!r} is not one of the configured model.heads {sorted(heads)}")
+            if pred2_head is not None and pred2_head not in heads:
+                raise ValueError(f"{where} pred2_head={pred2_head!r} is not one of the configured model.heads {sorted(heads)}")
+            if pred_head is None and primary is None and len(heads) > 1:
+                raise ValueError(f"{where} must define pred_head or model.primary_head when model.heads has multiple entries "
+                                 f"{sorted(heads)}")
+        elif pred_head is not None or pred2_head is not None:
+            raise ValueError(f"{where} uses pred_head/pred2_head but model.heads is not configured.")
+        pred_slice, pred2_slice = get("pred_slice", get("pred")), get("pred2_slice", get("pred2"))
+        if call_kind == "pred_only" and pred_slice is None:
+            raise ValueError(f"{where} pred_only terms require pred_slice")
+        if call_kind == "pred_pred" and (pred_slice is None or pred2_slice is None):
+            raise ValueError(f"{where} pred_pred terms require pred_slice and pred2_slice")
+        if pos_weight is not None and row.spatial != "weight":
+            raise ValueError(f"{where} pos_weight is only supported for losses with "
+                             f"spatial_weight_arg='weight' (got {fn})")
+        target_slice = get("target_slice", get("target"))
+        if target_slice is None and call_kind == "pred_target":
+            head = pred_head or primary or (next(iter(heads)) if len(heads) == 1 else None)
+            if head is not None:
+                target_slice = resolve_head_target_slice(cfg, head)
+        # the reference's spellings (training/losses/plan.py:126-147): coefficient = weight, pred / target / mask = *_slice
+        plan.append({"fn": fn, "row": row, "loss": loss, "weight": float(get("coefficient", get("weight", 1.0))),
+                     "pred_head": pred_head, "pred_slice": pred_slice, "call_kind": call_kind, "pred2_slice": pred2_slice,
+                     "pred2_head": pred2_head, "spatial_arg": row.spatial, "target_slice": target_slice, "pos_weight": pos_weight,
+                     "target_kind": row.target, "mask_slice": get("mask_slice", get("mask")),
+                     "apply_deep_supervision": bool(get("apply_deep_supervision", True)), "kwargs": kwargs})
+    return plan
+
+
 class ConnectomicsModule(nn.Module):
     def __init__(self, cfg, model: Optional[nn.Module] = None):
         super().__init__()
@@ -421,75 +255,7 @@ class ConnectomicsModule(nn.Module):
         loss_cfg = getattr(cfg.model, "loss", None)
         self.deep_supervision = bool(getattr(loss_cfg, "deep_supervision", False))
         self.ds_weights = list(getattr(loss_cfg, "deep_supervision_weights", None) or DS_WEIGHTS)
-        terms = getattr(loss_cfg, "losses", None)
-        if not terms:
-            terms = [{"function": "WeightedBCEWithLogitsLoss", "weight": 1.0},
-                     {"function": "DiceLoss", "weight": 1.0, "kwargs": {"sigmoid": True}}]
-        self.loss_terms = []
-        for t in terms:
-            get = (lambda k, d=None, _t=t: _t.get(k, d)) if isinstance(t, dict) else (lambda k, d=None, _t=t: getattr(_t, k, d))
-            fn = get("function")
-            if fn not in _LOSSES:
-                raise ValueError(f"Unknown loss function {fn!r}; available: {sorted(_LOSSES)}")
-            if fn == "SoftClDiceLoss":
-                SoftClDiceLoss(**dict(get("kwargs", None) or {}))      # its argument checks run when the module is built, as there
-            if fn == "ScnpLoss":
-                ScnpLoss(**dict(get("kwargs", None) or {}))
-            if fn in SOFTMAX_LOSSES:
-                SOFTMAX_LOSSES[fn][1](**dict(get("kwargs", None) or {}))
-            if _is_softmax_dice(fn, dict(get("kwargs", None) or {})):
-                check_softmax_dice_kwargs("DiceLoss", **dict(get("kwargs", None) or {}))
-            # how the loss is called (training/losses/plan.py:158-237): the kind is the loss's own; a term may restate it
-            where = f"losses[{len(self.loss_terms)}]"
-            own_kind, spatial_arg = _CALL_KINDS.get(fn, ("pred_target", None))
-            call_kind = str(get("call_kind", get("call", own_kind)))
-            if call_kind != own_kind:
-                raise ValueError(f"Unsupported call_kind {call_kind!r} in {where}")
-            loss_module = _LOSSES[fn](**dict(get("kwargs", None) or {})) if fn in _CALL_KINDS else None
-            pos_weight = get("pos_weight")
-            if isinstance(pos_weight, str):
-                if pos_weight.strip().lower() != "auto":
-                    raise ValueError(f"losses[{len(self.loss_terms)}] pos_weight must be a positive number or 'auto', got {pos_weight!r}")
-                pos_weight = "auto"
-            elif pos_weight is not None and float(pos_weight) <= 0:
-                raise ValueError(f"losses[{len(self.loss_terms)}] pos_weight must be > 0, got {float(pos_weight)}")
-            # which head a term reads is settled when the module is built (training/losses/plan.py:183-229): pred_head, else
-            # model.primary_head, else the only head; a term that names no target channels takes that head's `target_slice`
-            heads = getattr(cfg.model, "heads", None)
-            heads = heads if isinstance(heads, Mapping) else {}
-            pred_head, pred2_head, primary = get("pred_head"), get("pred2_head"), getattr(cfg.model, "primary_head", None)
-            if heads:
-                if pred_head is not None and pred_head not in heads:
-                    raise ValueError(f"{where} pred_head={pred_head!r} is not one of the configured model.heads {sorted(heads)}")
-                if pred2_head is not None and pred2_head not in heads:
-                    raise ValueError(f"{where} pred2_head={pred2_head!r} is not one of the configured model.heads {sorted(heads)}")
-                if pred_head is None and primary is None and len(heads) > 1:
-                    raise ValueError(f"{where} must define pred_head or model.primary_head when model.heads has multiple entries "
-                                     f"{sorted(heads)}")
-            elif pred_head is not None or pred2_head is not None:
-                raise ValueError(f"{where} uses pred_head/pred2_head but model.heads is not configured.")
-            pred_slice, pred2_slice = get("pred_slice", get("pred")), get("pred2_slice", get("pred2"))
-            if call_kind == "pred_only" and pred_slice is None:
-                raise ValueError(f"{where} pred_only terms require pred_slice")
-            if call_kind == "pred_pred" and (pred_slice is None or pred2_slice is None):
-                raise ValueError(f"{where} pred_pred terms require pred_slice and pred2_slice")
-            if pos_weight is not None and fn not in _WEIGHT_TAKING:
-                raise ValueError(f"{where} pos_weight is only supported for losses with "
-                                 f"spatial_weight_arg='weight' (got {fn})")
-            target_slice = get("target_slice", get("target"))
-            if target_slice is None and call_kind == "pred_target":
-                head = pred_head or primary or (next(iter(heads)) if len(heads) == 1 else None)
-                if head is not None:
-                    target_slice = resolve_head_target_slice(cfg, head)
-            # the reference's spellings (training/losses/plan.py:126-147): coefficient = weight, pred / target / mask = *_slice
-            self.loss_terms.append({"fn": fn, "weight": float(get("coefficient", get("weight", 1.0))), "pred_head": get("pred_head"),
-                                    "pred_slice": pred_slice, "call_kind": call_kind, "pred2_slice": pred2_slice,
-                                    "pred2_head": pred2_head, "spatial_arg": spatial_arg, "loss": loss_module,
-                                    "target_slice": target_slice, "pos_weight": pos_weight,
-                                    "target_kind": _TARGET_KINDS.get(fn, "dense"),
-                                    "mask_slice": get("mask_slice", get("mask")),
-                                    "apply_deep_supervision": bool(get("apply_deep_supervision", True)),
-                                    "kwargs": dict(get("kwargs", None) or {})})
+        self.loss_terms = plan_loss_terms(cfg)
         # adaptive loss balancing (reference training/losses/balancing.py:64-222; tutorials/mitoEM/common.yaml:54-55): a trainable
         # sub-module, every loss entry is one task.  `uncertainty` rides on the fused loss kernel (the learned task coefficients
         # enter it as host scalars, _balanced_scale_loss); `gradnorm` needs every task's own graph and takes the generic path
@@ -506,17 +272,14 @@ class ConnectomicsModule(nn.Module):
     def forward(self, x: torch.Tensor):
         return self.model(x)
 
-    _FUSABLE = {"WeightedBCEWithLogitsLoss": "bce", "BCEWithLogitsLoss": "bce", "DiceLoss": "dice"}
-
     def _term_is_fusable(self, t, pred) -> bool:
         """The fused kernel computes mean-reduced BCE-with-logits (numeric pos_weight) and sigmoid Dice with MONAI's default
         smoothing over all channels; any other variant of those terms takes the generic path."""
-        if t["fn"] not in self._FUSABLE or t.get("mask_slice") is not None:
+        kind = t["row"].fused
+        if kind is None or t.get("mask_slice") is not None:
             return False
         kw = t["kwargs"]
-        if _is_softmax_dice(t["fn"], kw):
-            return False
-        if self._FUSABLE[t["fn"]] == "bce":
+        if kind == "bce":
             return not isinstance(t["pos_weight"], str) and str(kw.get("reduction", "mean")) == "mean" and \
                 not (set(kw) - {"reduction"})
         smooth_ok = abs(float(kw.get("smooth_nr", 1e-5)) - 1e-5) < 1e-12 and abs(float(kw.get("smooth_dr", 1e-5)) - 1e-5) < 1e-12
@@ -531,7 +294,7 @@ class ConnectomicsModule(nn.Module):
         for i, t in terms:
             key = (str(t["pred_slice"]), str(t["target_slice"]))
             g = groups.setdefault(key, {"bce": None, "dice": None, "t": t})
-            kind = self._FUSABLE[t["fn"]]
+            kind = t["row"].fused
             if g[kind] is not None:
                 return None                   # two terms of one kind on the same slices: take the generic path
             g[kind] = (i, t)
@@ -545,7 +308,7 @@ class ConnectomicsModule(nn.Module):
                 y = target[:, resolve_channel_indices(t["target_slice"], num_channels=target.shape[1], context="target_slice")]
             wb = g["bce"][1]["weight"] if g["bce"] else 0.0
             wd = g["dice"][1]["weight"] if g["dice"] else 0.0
-            pw = g["bce"][1]["pos_weight"] if g["bce"] and g["bce"][1]["fn"] == "WeightedBCEWithLogitsLoss" else None
+            pw = g["bce"][1]["pos_weight"] if g["bce"] else None        # (None for a loss without a weight map: plan_loss_terms)
             v, out = bce_dice_loss(p, y, mask, w_bce=wb, w_dice=wd, pos_weight=pw)
             if g["bce"]:
                 parts[f"loss_{g['bce'][0]}_{g['bce'][1]['fn']}"] = out[1]
@@ -555,9 +318,9 @@ class ConnectomicsModule(nn.Module):
         return total, parts
 
     def _fusable(self, pred, mask, terms) -> bool:
-        # (torch's BCEWithLogitsLoss under a mask averages over ALL voxels -- masked ones as logit -20 / target 0 --, which the fused
-        # kernel's valid-voxel mean is not)
-        plain_bce_masked = mask is not None and any(t["fn"] == "BCEWithLogitsLoss" for _, t in terms)
+        # (a BCE that sees a mask through its inputs -- torch's BCEWithLogitsLoss -- averages over ALL voxels, masked ones as logit -20 /
+        # target 0, which the fused kernel's valid-voxel mean is not)
+        plain_bce_masked = mask is not None and any(t["row"].fused == "bce" and t["row"].spatial is None for _, t in terms)
         return bool(pred.is_cuda and self.fused_loss and not plain_bce_masked and all(self._term_is_fusable(t, pred) for _, t in terms))
 
     def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None, full_labels=None):
@@ -574,65 +337,17 @@ class ConnectomicsModule(nn.Module):
             # the terms without a target (regularisers) never enter the fused reduction and must not push the supervised terms off
             # it: those are judged on their own, the rest is added below
             # (nor do the softmax losses and L1Loss, which have kernels or rows of their own)
-            def on_fused(t):
-                return t.get("call_kind", "pred_target") == "pred_target" and t["fn"] not in SOFTMAX_LOSSES \
-                    and not _is_softmax_dice(t["fn"], t["kwargs"])
-            supervised = [(i, t) for i, t in terms if on_fused(t)]
+            supervised = [(i, t) for i, t in terms if not t["row"].beside_fused]
             if supervised and self._fusable(pred, mask, supervised):
                 res = self._fused_term_loss(pred, target, mask, supervised)      # finiteness is checked where fit() reads the value
                 if res is not None:
                     if len(supervised) == len(terms):
                         return res
                     total, parts = res
-                    terms = [(i, t) for i, t in terms if not on_fused(t)]
+                    terms = [(i, t) for i, t in terms if t["row"].beside_fused]
         for i, t in terms:
-            if t.get("call_kind", "pred_target") != "pred_target":
-                v = self._regularizer_loss(i, t, pred, target, mask, heads)
-                parts[f"loss_{i}_{t['fn']}"] = v.detach()
-                if tasks is not None:
-                    tasks[i] = t["weight"] * v
-                total = total + t["weight"] * v
-                continue
-            p, y = pred, target
-            if t["pred_slice"] is not None:
-                p = pred[:, resolve_channel_indices(t["pred_slice"], num_channels=pred.shape[1], context="pred_slice")]
-            if t.get("target_kind", "dense") == "class_index" and full_labels is not None:
-                y = full_labels
-            if t["target_slice"] is not None:
-                y = y[:, resolve_channel_indices(t["target_slice"], num_channels=y.shape[1], context="target_slice")]
-            if t.get("target_kind", "dense") == "class_index":
-                if y.dim() != pred.dim() or y.shape[1] != 1:
-                    raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' takes a class-index target of one channel, got "
-                                     f"{tuple(y.shape)} (name it with target_slice)")
-                y = resize_class_index_to_output(y, pred)
-            # what the loss sees as its spatial argument (reference orchestrator.py:566-646): a term's own mask channels
-            # (`mask_slice` of the labels) x the batch mask; a `weight`-taking loss without a mask of its own gets the
-            # class-balancing map instead (not the weighted BCE, whose pos_weight is a scalar of its own)
-            own = None
-            if t.get("mask_slice") is not None:
-                own = target[:, resolve_channel_indices(t["mask_slice"], num_channels=target.shape[1], context="mask_slice")]
-            valid = own if mask is None else (mask if own is None else own * mask)
-            fn = t["fn"]
-            if fn in _WEIGHT_TAKING:
-                spatial = own
-                if spatial is None and fn != "WeightedBCEWithLogitsLoss":
-                    spatial = class_balance_weight(y, 1.0 if (t["pos_weight"] is None and fn in _OWN_CLASS_BALANCE) else t["pos_weight"],
-                                                   valid_mask=valid)
-                if mask is not None:
-                    spatial = mask if spatial is None else spatial * mask
-                pw = t["pos_weight"] if fn == "WeightedBCEWithLogitsLoss" else None
-                if isinstance(pw, str):
-                    pw = auto_pos_weight_scalar(y, valid)
-                elif pw is not None and float(pw) == 1.0:
-                    pw = None
-                v = _LOSSES[fn](p, y, weight=spatial, pos_weight=pw, clamp_min=self.clamp_min, **t["kwargs"])
-            elif _is_softmax_dice(fn, t["kwargs"]):
-                v = softmax_dice_loss(p, y, valid, fill=self.clamp_min, **t["kwargs"])
-            elif fn in SOFTMAX_LOSSES:
-                # the mask goes by position: `weight` in the term's kwargs is the CLASS weight of CrossEntropyLoss / DiceCELoss
-                v = _LOSSES[fn](p, y, valid, fill=self.clamp_min, **t["kwargs"])
-            else:
-                v = _LOSSES[fn](p, y, weight=valid, pos_weight=None, clamp_min=self.clamp_min, **t["kwargs"])
+            v = self._supervised_loss(i, t, pred, target, mask, full_labels) if t["row"].call == "pred_target" else \
+                self._regularizer_loss(i, t, pred, target, mask, heads)
             if not torch.isfinite(v):
                 raise FloatingPointError(f"loss term {t['fn']} is not finite")
             parts[f"loss_{i}_{t['fn']}"] = v.detach()
@@ -640,6 +355,44 @@ class ConnectomicsModule(nn.Module):
                 tasks[i] = t["weight"] * v
             total = total + t["weight"] * v
         return total, parts
+
+    def _supervised_loss(self, i, t, pred, target, mask, full_labels):
+        """A `pred_target` term on the clamped predictions: its slices, its target form and its spatial argument."""
+        row = t["row"]
+        p, y = pred, target
+        if t["pred_slice"] is not None:
+            p = pred[:, resolve_channel_indices(t["pred_slice"], num_channels=pred.shape[1], context="pred_slice")]
+        if row.target == "class_index" and full_labels is not None:
+            y = full_labels
+        if t["target_slice"] is not None:
+            y = y[:, resolve_channel_indices(t["target_slice"], num_channels=y.shape[1], context="target_slice")]
+        if row.target == "class_index":
+            if y.dim() != pred.dim() or y.shape[1] != 1:
+                raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' takes a class-index target of one channel, got "
+                                 f"{tuple(y.shape)} (name it with target_slice)")
+            y = resize_class_index_to_output(y, pred)
+        # what the loss sees as its spatial argument (reference orchestrator.py:566-646): a term's own mask channels
+        # (`mask_slice` of the labels) x the batch mask; a `weight`-taking loss without a mask of its own gets the
+        # class-balancing map instead (unless its pos_weight is a scalar of its own)
+        own = None
+        if t.get("mask_slice") is not None:
+            own = target[:, resolve_channel_indices(t["mask_slice"], num_channels=target.shape[1], context="mask_slice")]
+        valid = own if mask is None else (mask if own is None else own * mask)
+        if row.spatial != "weight":
+            return t["loss"](p, y, valid, fill=self.clamp_min)
+        spatial, pw = own, None
+        if spatial is None and row.balance_map:
+            spatial = class_balance_weight(y, 1.0 if (t["pos_weight"] is None and row.own_pos_weight) else t["pos_weight"],
+                                           valid_mask=valid)
+        if mask is not None:
+            spatial = mask if spatial is None else spatial * mask
+        if not row.balance_map:
+            pw = t["pos_weight"]
+            if isinstance(pw, str):
+                pw = auto_pos_weight_scalar(y, valid)
+            elif pw is not None and float(pw) == 1.0:
+                pw = None
+        return t["loss"](p, y, spatial, fill=self.clamp_min, pos_weight=pw)
 
     def _regularizer_loss(self, i, t, pred, target, mask, heads):
         """A `pred_only` / `pred_pred` term (training/losses/orchestrator.py:533-718): one or two slices of the clamped predictions
@@ -663,8 +416,6 @@ class ConnectomicsModule(nn.Module):
             v = t["loss"](*args, mask=combined)
         else:
             v = t["loss"](*args)
-        if not torch.isfinite(v):
-            raise FloatingPointError(f"loss term {t['fn']} is not finite")
         return v
 
     def _balanced_scale_loss(self, items, stage: str, heads=None, full_labels=None):

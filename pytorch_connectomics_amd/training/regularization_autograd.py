@@ -26,36 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-
-def _checked_mask(mask: Optional[torch.Tensor], loss_shape, name: str) -> Optional[torch.Tensor]:
-    """The mask as given, after the check that it broadcasts TO the loss (never enlarges it)."""
-    if mask is None:
-        return None
-    try:
-        ok = tuple(torch.broadcast_shapes(tuple(loss_shape), tuple(mask.shape))) == tuple(loss_shape)
-    except RuntimeError:
-        ok = False
-    if not ok:
-        raise ValueError(f"{name}: mask of shape {tuple(mask.shape)} does not broadcast to the loss of shape {tuple(loss_shape)}")
-    return mask
-
-
-def _wants_hip(use_hip: Optional[bool], x: torch.Tensor, name: str) -> bool:
-    hip = x.is_cuda if use_hip is None else bool(use_hip)
-    if hip and not x.is_cuda:
-        raise RuntimeError(f"{name}(use_hip=True) needs CUDA(HIP) tensors: the HIP kernels have no CPU path")
-    return hip
-
-
-def _kernel_mask(mask: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
-    """The mask as the kernels read it: fp32 contiguous with the operand's channels or one; any other shape that broadcasts to the
-    operand's is expanded first."""
-    if mask is None:
-        return None
-    m = mask.detach().float()
-    if m.dim() != like.dim() or m.shape[1] not in (1, like.shape[1]) or m.shape[0] != like.shape[0] or m.shape[2:] != like.shape[2:]:
-        m = m.expand_as(like)
-    return m.contiguous()
+from .hip_dispatch import checked_mask, kernel_mask, wants_hip
 
 
 # ---- the torch restatements (the CPU path, and the yardstick of the GPU tests) -----------------------------------------------------
@@ -194,13 +165,13 @@ class BinaryRegularization(nn.Module):
         self.use_hip = use_hip
 
     def forward(self, pred: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        mask = _checked_mask(mask, pred.shape, "BinaryRegularization")
-        if not _wants_hip(self.use_hip, pred, "BinaryRegularization"):
+        mask = checked_mask(mask, pred.shape, "BinaryRegularization")
+        if not wants_hip(self.use_hip, pred, "BinaryRegularization"):
             return binary_regularization_torch(pred, mask, min_threshold=self.min_threshold, apply_sigmoid=self.apply_sigmoid)
         if pred.dim() < 2:
             raise ValueError(f"BinaryRegularization expects (N, C, ...) predictions, got {tuple(pred.shape)}")
         x = _operand(pred)
-        return _BinaryRegularizationFn.apply(x, None, _kernel_mask(mask, x), float(self.min_threshold), bool(self.apply_sigmoid), x.numel())
+        return _BinaryRegularizationFn.apply(x, None, kernel_mask(mask, x), float(self.min_threshold), bool(self.apply_sigmoid), x.numel())
 
 
 class ForegroundDistanceConsistency(nn.Module):
@@ -212,11 +183,11 @@ class ForegroundDistanceConsistency(nn.Module):
 
     def forward(self, foreground_logits: torch.Tensor, distance_transform: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         shape = torch.broadcast_shapes(tuple(foreground_logits.shape), tuple(distance_transform.shape))
-        mask = _checked_mask(mask, shape, "ForegroundDistanceConsistency")
-        if not _wants_hip(self.use_hip, foreground_logits, "ForegroundDistanceConsistency"):
+        mask = checked_mask(mask, shape, "ForegroundDistanceConsistency")
+        if not wants_hip(self.use_hip, foreground_logits, "ForegroundDistanceConsistency"):
             return foreground_distance_consistency_torch(foreground_logits, distance_transform, mask)
         a, b = _two_operands("ForegroundDistanceConsistency", foreground_logits, distance_transform)
-        return _ForegroundDistanceFn.apply(a, b, _kernel_mask(mask, a), 0.0, True, a.numel())
+        return _ForegroundDistanceFn.apply(a, b, kernel_mask(mask, a), 0.0, True, a.numel())
 
 
 class ContourDistanceConsistency(nn.Module):
@@ -229,11 +200,11 @@ class ContourDistanceConsistency(nn.Module):
     def forward(self, contour_logits: torch.Tensor, distance_transform: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         if contour_logits.shape != distance_transform.shape:
             raise ValueError(f"Shape mismatch: contour_prob={contour_logits.shape} vs distance_abs={distance_transform.shape}")
-        mask = _checked_mask(mask, contour_logits.shape, "ContourDistanceConsistency")
-        if not _wants_hip(self.use_hip, contour_logits, "ContourDistanceConsistency"):
+        mask = checked_mask(mask, contour_logits.shape, "ContourDistanceConsistency")
+        if not wants_hip(self.use_hip, contour_logits, "ContourDistanceConsistency"):
             return contour_distance_consistency_torch(contour_logits, distance_transform, mask)
         a, b = _two_operands("ContourDistanceConsistency", contour_logits, distance_transform)
-        return _ContourDistanceFn.apply(a, b, _kernel_mask(mask, a), 0.0, True, a.numel())
+        return _ContourDistanceFn.apply(a, b, kernel_mask(mask, a), 0.0, True, a.numel())
 
 
 class ForegroundContourConsistency(nn.Module):
@@ -254,15 +225,15 @@ class ForegroundContourConsistency(nn.Module):
         if foreground_logits.dim() != 5 or foreground_logits.shape[1] != 1:
             raise ValueError("ForegroundContourConsistency takes 5-D single-channel foreground logits (N, 1, D, H, W), got "
                              f"{tuple(foreground_logits.shape)}")
-        hip = _wants_hip(self.use_hip, foreground_logits, "ForegroundContourConsistency")
+        hip = wants_hip(self.use_hip, foreground_logits, "ForegroundContourConsistency")
         if self.kernel_size != 3 or contour_logits.shape != foreground_logits.shape or not hip:
             # (any kernel size but 3, or a contour map of another shape, ends in the reference's shape-mismatch error)
             if self.kernel_size == 3 and contour_logits.shape == foreground_logits.shape:
-                mask = _checked_mask(mask, foreground_logits.shape, "ForegroundContourConsistency")
+                mask = checked_mask(mask, foreground_logits.shape, "ForegroundContourConsistency")
             return foreground_contour_consistency_torch(foreground_logits, contour_logits, mask, kernel_size=self.kernel_size, eps=self.eps)
-        mask = _checked_mask(mask, foreground_logits.shape, "ForegroundContourConsistency")
+        mask = checked_mask(mask, foreground_logits.shape, "ForegroundContourConsistency")
         fg = _operand(foreground_logits)
-        return _ForegroundContourFn.apply(fg, _operand(contour_logits), _kernel_mask(mask, fg), float(self.eps))
+        return _ForegroundContourFn.apply(fg, _operand(contour_logits), kernel_mask(mask, fg), float(self.eps))
 
 
 class NonOverlapRegularization(nn.Module):
@@ -276,20 +247,11 @@ class NonOverlapRegularization(nn.Module):
     def forward(self, pred: torch.Tensor) -> torch.Tensor:
         if pred.dim() < 2 or pred.shape[1] < 2:
             raise ValueError(f"Expected at least 2 channels for pre/post predictions, got {pred.shape[1] if pred.dim() >= 2 else 0}")
-        if not _wants_hip(self.use_hip, pred, "NonOverlapRegularization"):
+        if not wants_hip(self.use_hip, pred, "NonOverlapRegularization"):
             return non_overlap_regularization_torch(pred, cleft_masked=self.cleft_masked)
         x = _operand(pred)
         return _NonOverlapFn.apply(x, None, None, 0.0, bool(self.cleft_masked), x.numel() // x.shape[1])
 
 
-# name -> (class, call kind, spatial argument): models/losses/metadata.py:53-76
-REGULARIZATION_LOSSES = {
-    "BinaryRegularization": (BinaryRegularization, "pred_only", "mask"),
-    "NonOverlapRegularization": (NonOverlapRegularization, "pred_only", None),
-    "ForegroundDistanceConsistency": (ForegroundDistanceConsistency, "pred_pred", "mask"),
-    "ContourDistanceConsistency": (ContourDistanceConsistency, "pred_pred", "mask"),
-    "ForegroundContourConsistency": (ForegroundContourConsistency, "pred_pred", "mask"),
-}
-
 __all__ = ["BinaryRegularization", "ForegroundDistanceConsistency", "ContourDistanceConsistency", "ForegroundContourConsistency",
-           "NonOverlapRegularization", "REGULARIZATION_LOSSES"]
+           "NonOverlapRegularization"]

@@ -18,6 +18,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .hip_dispatch import kernel_mask, wants_hip
+from .losses import per_channel_bce_with_logits
+
 _LARGE = 9999.0
 
 
@@ -102,21 +105,12 @@ class ScnpLoss(nn.Module):
     def forward(self, input: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         if input.ndim not in (4, 5):
             raise ValueError(f"ScnpLoss expects 4D [B,C,H,W] or 5D [B,C,Z,Y,X] logits, got {input.ndim}D.")
-        hip = input.is_cuda if self.use_hip is None else bool(self.use_hip)
-        if hip and not input.is_cuda:
-            raise RuntimeError("ScnpLoss(use_hip=True) needs CUDA(HIP) tensors: the HIP kernels have no CPU path")
         x, t = input.float(), target.float()
-        if not hip:
-            from .module import per_channel_bce_with_logits
+        if not wants_hip(self.use_hip, input, "ScnpLoss"):
             return per_channel_bce_with_logits(scnp_logits_torch(x, t, self.neighborhood_size), t, weight,
                                                auto_pos_weight=self.auto_pos_weight, max_pos_weight=self.max_pos_weight,
                                                reduction=self.reduction)
-        w = None
-        if weight is not None:
-            w = weight.detach().float()
-            if w.dim() != x.dim() or w.shape[1] not in (1, x.shape[1]) or w.shape[0] != x.shape[0] or w.shape[2:] != x.shape[2:]:
-                w = w.expand_as(x)                     # another broadcastable shape, e.g. (1, C, 1, 1, 1)
-            w = w.contiguous()
+        w = kernel_mask(weight, x)                     # (another broadcastable shape, e.g. (1, C, 1, 1, 1), is expanded)
         mean = self.reduction == "mean"
         # 'mean' averages weight * bce over the voxels of weight > 0; 'sum' adds every voxel's weight * bce, whatever its sign
         bce, valid = _ScnpSums.apply(x.contiguous(), t.detach().contiguous(), w, self.neighborhood_size, self.auto_pos_weight,
@@ -126,8 +120,3 @@ class ScnpLoss(nn.Module):
             per_channel = per_channel / valid.sum(0).clamp_min(1).float()
         return per_channel.sum()
 
-
-def scnp_term(pred, target, weight=None, **kwargs):
-    """The `ScnpLoss` term of ConnectomicsModule: the loss with the term's kwargs and the spatial weight the orchestrator hands it
-    (the term's own mask, or the class-balancing map: models/losses/metadata.py:45)."""
-    return ScnpLoss(**kwargs)(pred, target, weight=weight)

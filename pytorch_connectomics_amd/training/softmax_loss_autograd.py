@@ -27,6 +27,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
+from .hip_dispatch import channel_mask, wants_hip
+
 SUM_COLUMNS = ("pt", "p", "pp", "t", "tt", "ce", "nlogp", "t_valid")
 
 
@@ -43,22 +45,12 @@ def target_form(logits: torch.Tensor, target: torch.Tensor):
                      "channel or without one")
 
 
-def _checked_mask(mask, logits):
-    if mask is None:
-        return None
-    if mask.dim() != logits.dim() or mask.shape[0] != logits.shape[0] or mask.shape[1] not in (1, logits.shape[1]) \
-            or mask.shape[2:] != logits.shape[2:]:
-        mask = mask.expand(logits.shape[:1] + (1,) + logits.shape[2:]) if mask.dim() == logits.dim() and mask.shape[1] == 1 \
-            else mask.expand_as(logits)
-    return mask
-
-
 def softmax_loss_sums_torch(logits, target, mask=None, *, ignore_index: int = -100, fill: float = -20.0):
     """The eight columns in plain torch, in the logits' dtype, for any C (the CPU path and the yardstick of the GPU tests)."""
     x = logits
     C = x.shape[1]
     form, tgt = target_form(x, target)
-    mask = _checked_mask(mask, x)
+    mask = channel_mask(mask, x)
     live = None
     if mask is not None:
         live = (mask > 0).expand_as(x)
@@ -113,10 +105,7 @@ def softmax_loss_sums(logits, target, mask=None, *, ignore_index: int = -100, fi
     """-> (N, C, 8) sums (see the module docstring), differentiable in the logits."""
     if logits.dim() < 3:
         raise ValueError(f"softmax losses expect (N, C, *spatial) logits, got {tuple(logits.shape)}")
-    hip = logits.is_cuda if use_hip is None else bool(use_hip)
-    if hip and not logits.is_cuda:
-        raise RuntimeError("softmax_loss_sums(use_hip=True) needs CUDA(HIP) tensors: the HIP kernels have no CPU path")
-    if not hip:
+    if not wants_hip(use_hip, logits, "softmax_loss_sums"):
         return softmax_loss_sums_torch(logits, target, mask, ignore_index=ignore_index, fill=fill)
     C = int(logits.shape[1])
     if not 2 <= C <= 32:
@@ -128,9 +117,8 @@ def softmax_loss_sums(logits, target, mask=None, *, ignore_index: int = -100, fi
         tgt = tgt.float()
     elif tgt.dtype != torch.int64:
         tgt = tgt.long()
-    mask = _checked_mask(mask, logits)
     if mask is not None:
-        mask = mask.detach().float()
+        mask = channel_mask(mask.detach().float(), logits)          # in its own layout: the kernels take strides
     return SoftmaxLossSumsFn.apply(logits.float(), tgt, mask, int(ignore_index), float(fill))
 
 
@@ -224,7 +212,7 @@ def softmax_dice_loss(logits, target, mask=None, *, fill: float = -20.0, include
     else:
         x = logits
         C = x.shape[1]
-        m = _checked_mask(mask, x)
+        m = channel_mask(mask, x)
         y = tgt.long()
         if m is not None:
             live = (m > 0).expand_as(x)
@@ -327,13 +315,5 @@ def l1_loss(pred, target, mask=None, *, fill: float = -20.0, reduction: str = "m
     return F.l1_loss(p, t, reduction=reduction)
 
 
-# name -> (term function (pred, target, mask, fill=..., **kwargs), kwargs check run when the module is built, target kind)
-SOFTMAX_LOSSES = {
-    "CrossEntropyLoss": (cross_entropy_loss, check_cross_entropy_kwargs, "class_index"),
-    "DiceCELoss": (dice_ce_loss, check_dice_ce_kwargs, "dense"),
-    "GeneralizedDiceLoss": (generalized_dice_loss, check_generalized_dice_kwargs, "dense"),
-    "L1Loss": (l1_loss, check_l1_kwargs, "dense"),
-}
-
 __all__ = ["softmax_loss_sums", "softmax_loss_sums_torch", "target_form", "cross_entropy_loss", "softmax_dice_loss", "dice_ce_loss",
-           "generalized_dice_loss", "l1_loss", "SOFTMAX_LOSSES", "SUM_COLUMNS"]
+           "generalized_dice_loss", "l1_loss", "SUM_COLUMNS"]

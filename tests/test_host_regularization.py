@@ -89,8 +89,8 @@ def test_hip_backend_refuses_cpu_tensors(name):
 @pytest.mark.parametrize("which", sorted(RC.ORCH_TERMS))
 def test_term_plan_matches_the_reference_planner(gold, which):
     m = _module(RC.orch_cfg(which))
-    from pytorch_connectomics_amd.training.module import _WEIGHT_TAKING
-    got = [f"{t['call_kind']}|{'weight' if t['fn'] in _WEIGHT_TAKING else t['spatial_arg']}|{t['pred_slice']}|{t['pred2_slice']}|"
+    from pytorch_connectomics_amd.training.loss_table import LOSS_TABLE
+    got = [f"{t['call_kind']}|{LOSS_TABLE[t['fn']].spatial}|{t['pred_slice']}|{t['pred2_slice']}|"
            f"{t['pred2_head']}|{t['mask_slice']}|{t['apply_deep_supervision']}" for t in m.loss_terms]
     assert got == [str(s) for s in gold[f"orch_{which}__plan"]]
 

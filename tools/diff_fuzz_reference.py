@@ -401,7 +401,8 @@ def training_host_side(t, rnd):
         if not n.startswith("_"):
             setattr(sys.modules["connectomics.models.losses"], n, getattr(meta, n))
     plan = S.ref("connectomics.training.losses.plan")
-    reg_names = sorted(ora.REGULARIZATION_LOSSES)
+    from pytorch_connectomics_amd.training.loss_table import LOSS_TABLE
+    reg_names = sorted(n for n, row in LOSS_TABLE.items() if row.call != "pred_target")
 
     def plan_cfg(terms, heads):
         return NS(model=NS(loss=NS(deep_supervision=False, deep_supervision_weights=[1.0], deep_supervision_clamp_min=-20.0,
