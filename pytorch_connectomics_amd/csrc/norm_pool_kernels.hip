@@ -125,7 +125,7 @@ maxpool3d_kernel(const T* __restrict__ x, T* __restrict__ y, int D, int H, int W
   const int oz = (int)(t % Do);
   const long n = t / Do;
   const T* xn = x + n * (long)D * H * W * C;
-  float m = -3.402823466e38f;
+  float m = -INFINITY;          // a window that is all -inf stays -inf (nn.MaxPool3d; maxpool3d_bwd_kernel starts there too)
   for (int a = 0; a < fz; ++a)
     for (int b = 0; b < fy; ++b)
       for (int d = 0; d < fx; ++d)
