@@ -272,8 +272,9 @@ int pytc_dwconv3d_fwd_res(const void* x, const void* res, void* y, const float* 
 /* Depthwise ConvTranspose3d (groups == C), kernel K^3, stride 2, padding K/2 -> Do = 2D-1.
  * Replaces MedNeXtUpBlock.conv1.  Output is written into a buffer of spatial size
  * (2D)x(2H)x(2W) at offset +1 on every axis (the block's later F.pad((1,0,1,0,1,0)) is thereby
- * free); the front faces of y are NOT touched.  w fp32 [K^3][C] with
- * w[(kz*K+ky)*K+kx][c] = torch_weight[c][0][kz][ky][kx].  stats as above, over (2D-1)^3. */
+ * free); the front faces of y (position 0 of an axis) are written as ZERO by every form (cell, tile, generic).
+ * w fp32 [K^3][C] with w[(kz*K+ky)*K+kx][c] = torch_weight[c][0][kz][ky][kx].  stats as above, over (2D-1)^3 (the zero faces add
+ * nothing).  y = NULL (K = 3, statistics given): the statistics-only pass of the cell and tile forms. */
 int pytc_dwconvT3d_fwd(const void* x, void* y, const float* w, const float* bias, float* stats,
                        int N, int D, int H, int W, int C, int K, int dtype, void* stream);
 

@@ -1823,7 +1823,10 @@ def norm_bwd(dtn: torch.Tensor, t: torch.Tensor, mean_rstd: torch.Tensor, gamma:
 
 
 def dwconv3d_bwd_data(dy: torch.Tensor, w_taps: torch.Tensor, xdims, *, K: int, stride: int, add: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Data gradient of a (strided) depthwise conv; add (shaped like the result): dx = conv^T(dy) + add in the same launch."""
+    """Data gradient of a (strided) depthwise conv; add (shaped like the result): dx = conv^T(dy) + add in the same launch.  `add` joins
+    the fp32 accumulator after the last tap (dwconv_bwd_data_vec_kernel: acc[q] += av[q], then the store): ONE rounding to the storage
+    type, where the convolution followed by add_ has two.  `add` needs 16-byte channel groups (the vector kernel); without it
+    C % 8 != 0 (bf16) / C % 4 != 0 (fp32) takes the scalar kernel -- same taps in the same (kz, ky, kx) order."""
     _dev(dy, "dy")
     N, Cc = dy.shape[0], dy.shape[-1]
     dx = torch.empty((N, *[int(v) for v in xdims], Cc), dtype=dy.dtype, device=dy.device)
