@@ -32,8 +32,9 @@ extern "C" {
  * 8: pytc_scnp_* (the neighbour-penalised logits of ScnpLoss, its BCE sums and its gradient).
  * 9: pytc_reg_* and pytc_fgcontour_* (the regularisation losses: streaming sums and gradients, the foreground / contour stencil).
  * 10: pytc_softmax_loss_* (the channel softmax reduced to eight sums per (sample, class), and its gradient: the softmax losses).
+ * 11: pytc_confusion_* (logits and labels counted into a K x K table of int64: the jaccard / dice / accuracy evaluation metrics).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 10
+#define PYTC_ABI_VERSION 11
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1041,6 +1042,32 @@ int pytc_softmax_loss_forward(const float* x, const void* target, const float* m
 int pytc_softmax_loss_backward(const float* x, const void* target, const float* mask, const float* gsums, float* dx, int N, int C,
                                int64_t R, const int64_t* x_strides, const int64_t* t_strides, const int64_t* m_strides,
                                const int64_t* d_strides, int target_kind, int64_t ignore_index, float fill, void* stream);
+
+/* The evaluation metrics (training/lightning/model.py:434-476, 912-1005; evaluation/metric_execution.py:166-220): jaccard, dice and
+ * accuracy, binary or multi-class, are functions of a K x K table of voxel counts, K = max(C, 2).  One streaming pass makes it.
+ * x is fp32 (N, C, R) addressed by x_strides = (stride_n, stride_c, stride_r), exactly as in pytc_softmax_loss_forward; 1 <= C <= 32,
+ * another C returns PYTC_ERR_UNSUPPORTED.
+ * Predicted class p: C == 1: x > pred_threshold (strict; NaN gives 0).  C >= 2: the first index of the maximum, NaN counting as the
+ *   maximum ([inf, nan, inf] -> 1, [2, 2, 1] -> 0: torch.argmax on the CPU).
+ * Target class t, target_dtype PYTC_TARGET_F32 / _I64 / _U8, t_strides = (stride_n, stride_c, stride_r) (stride_c unused unless dense):
+ *   PYTC_CONFUSION_INDEX: (N, R) class indices, a float truncated toward zero (-0.5 -> 0, 1.9 -> 1);
+ *   PYTC_CONFUSION_THRESHOLD: C == 1 only, t = target > target_threshold;
+ *   PYTC_CONFUSION_DENSE: C >= 2, fp32 (N, C, R) only, t = argmax by the rule of the prediction.
+ * counts: K * K + 1 int64.  The call ADDS the number of voxels with target t and prediction p to counts[t * K + p], and the number
+ *   of voxels whose index target lies outside [0, K) (or is not finite) to counts[K * K]; those enter no cell.  The caller zeroes
+ *   counts when an epoch starts.  partial: N * pytc_confusion_tiles(R) * (K * K + 1) uint32 of per-tile rows, written with plain
+ *   stores; a second launch adds them in int64.  Integers only: any order of the adds gives the same table.  Nothing synchronises
+ *   with the host. */
+#define PYTC_TARGET_F32 0
+#define PYTC_TARGET_I64 1
+#define PYTC_TARGET_U8 2
+#define PYTC_CONFUSION_INDEX 0
+#define PYTC_CONFUSION_THRESHOLD 1
+#define PYTC_CONFUSION_DENSE 2
+int pytc_confusion_tiles(int64_t R);
+int pytc_confusion_counts(const float* x, const void* target, uint32_t* partial, int64_t* counts, int N, int C, int64_t R,
+                          const int64_t* x_strides, const int64_t* t_strides, int target_dtype, int target_mode, float pred_threshold,
+                          float target_threshold, void* stream);
 
 #ifdef __cplusplus
 }

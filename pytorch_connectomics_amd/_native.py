@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 10        # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 11        # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -314,6 +314,9 @@ _SIGS = {
                                   + [C.c_int, C.c_int64, C.c_float, C.c_void_p]),
     "pytc_softmax_loss_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int64)] * 4
                                    + [C.c_int, C.c_int64, C.c_float, C.c_void_p]),
+    "pytc_confusion_tiles": (C.c_int, [C.c_int64]),
+    "pytc_confusion_counts": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int64)] * 2
+                              + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "pytc_reg_tiles": (C.c_int, [C.c_int64]),
     "pytc_reg_pointwise_forward": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "pytc_reg_pointwise_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),

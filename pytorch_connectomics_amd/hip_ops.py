@@ -2663,3 +2663,58 @@ def softmax_loss_backward(gsums: torch.Tensor, x: torch.Tensor, target: torch.Te
          _p(gsums), _p(dx), N, C_, R, xs, ts, ms, (C.c_int64 * 3)(*ds), kind, int(ignore_index), float(fill), _stream(),
          symbol="softmax_loss_backward")
     return dx
+
+
+# ---- evaluation metrics: logits and labels counted into a K x K table of int64 (csrc/metric_kernels.hip) ----
+CONFUSION_MAX_C = 32
+CONFUSION_TARGET_MODES = {"index": 0, "threshold": 1, "dense": 2}
+_CONFUSION_TARGET_DTYPES = {torch.float32: 0, torch.int64: 1, torch.uint8: 2}
+
+
+def confusion_counts(x: torch.Tensor, target: torch.Tensor, counts: Optional[torch.Tensor] = None, *, target_mode: str = "index",
+                     pred_threshold: float = 0.5, target_threshold: float = 0.5, _partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """counts (K * K + 1 int64, K = max(C, 2)) += the voxels of x (fp32 (N, C, *spatial), any layout whose spatial dims collapse, read
+    uncopied) with target class t and predicted class p at [t * K + p], and the voxels with an index label outside [0, K) at [K * K]
+    (include/pytc_hip.h pytc_confusion_counts).  target: "index" / "threshold" (C == 1) as fp32, int64 or uint8 of shape (N, *spatial)
+    or (N, 1, *spatial); "dense" (C >= 2) as fp32 of x's shape.  `counts` None starts a zeroed table.  Two launches, no torch
+    element-wise op, no host synchronisation.  `_partial` lets a test supply a guarded allocation."""
+    for name, t in (("prediction", x), ("target", target)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA(HIP) tensor: pytorch_connectomics_amd has no CPU path")
+    if x.dtype != torch.float32 or x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"the prediction must be non-empty float32 of shape (N, C, *spatial), got {x.dtype} {tuple(x.shape)}")
+    N, C_ = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= C_ <= CONFUSION_MAX_C:
+        raise NotImplementedError(f"the count kernels cover 1 <= C <= {CONFUSION_MAX_C} classes, got C = {C_} (CPU tensors take any C)")
+    if target_mode not in CONFUSION_TARGET_MODES:
+        raise ValueError(f"target_mode must be one of {sorted(CONFUSION_TARGET_MODES)}, got {target_mode!r}")
+    if target.dtype not in _CONFUSION_TARGET_DTYPES:
+        raise ValueError(f"the target must be float32, int64 or uint8, got {target.dtype}")
+    if target_mode == "dense":
+        if C_ < 2 or target.shape != x.shape or target.dtype != torch.float32:
+            raise ValueError(f"a dense target needs C >= 2 and float32 of the prediction's shape {tuple(x.shape)}, got {target.dtype} "
+                             f"{tuple(target.shape)}")
+    else:
+        if target_mode == "threshold" and C_ != 1:
+            raise ValueError(f"a threshold target needs a one-channel prediction, got C = {C_}")
+        if target.shape == x.shape[:1] + x.shape[2:]:
+            target = target.unsqueeze(1)
+        if target.shape != x.shape[:1] + (1,) + x.shape[2:]:
+            raise ValueError(f"target of shape {tuple(target.shape)} does not hold one class per voxel of the prediction {tuple(x.shape)}")
+    K = max(C_, 2)
+    R = x.numel() // (N * C_)
+    x, xs = _strided(x)
+    t, ts = _strided(target)
+    lib = nat.lib()
+    n_part = N * lib.pytc_confusion_tiles(R) * (K * K + 1)
+    part = torch.empty((n_part,), dtype=torch.int32, device=x.device) if _partial is None else _partial
+    if part.numel() != n_part or part.dtype != torch.int32 or not part.is_contiguous():
+        raise ValueError(f"_partial must hold {n_part} contiguous int32")
+    if counts is None:
+        counts = torch.zeros((K * K + 1,), dtype=torch.int64, device=x.device)
+    if not counts.is_cuda or counts.dtype != torch.int64 or tuple(counts.shape) != (K * K + 1,) or not counts.is_contiguous():
+        raise ValueError(f"counts must be a contiguous int64 CUDA(HIP) tensor of {K * K + 1} elements for C = {C_}")
+    _run(f"confusion_counts[C={C_}]", _nbytes(x, t), lib.pytc_confusion_counts, _p(x), _p(t), _p(part), _p(counts), N, C_, R, xs, ts,
+         _CONFUSION_TARGET_DTYPES[t.dtype], CONFUSION_TARGET_MODES[target_mode], float(pred_threshold), float(target_threshold), _stream(),
+         symbol="confusion_counts")
+    return counts

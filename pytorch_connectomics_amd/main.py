@@ -130,6 +130,38 @@ def binary_jaccard(pred: torch.Tensor, label: torch.Tensor, threshold: float = 0
     return float(inter) / float(union) if union else 1.0
 
 
+INSTANCE_METRICS = ("adapted_rand", "voi", "instance_accuracy", "instance_accuracy_detail", "nerl")
+
+
+def voxel_metrics(pred: torch.Tensor, label: torch.Tensor, names=None, threshold: float = 0.5) -> dict:
+    """The test-mode voxel metrics of one prediction channel against a label volume of its shape, from one table of counts
+    (training/metrics.py): a device prediction is counted on the device by the HIP kernel, a host array by torch on the CPU.
+    names None (evaluation off): {"jaccard"} as `binary_jaccard` defines it (pred > 0.5, label > 0, 1.0 for an empty union).
+    names given: those of jaccard / dice / accuracy with the rules of the reference's compute_binary_metrics
+    (evaluation/metric_execution.py:166-220): a prediction with max <= 1 is thresholded directly, any other through a sigmoid
+    (taken as pred > logit(threshold)); a label with max <= 1 is thresholded at `threshold`, any other at 0."""
+    import math
+    from .training.metrics import ConfusionState, metrics_from_counts
+    if tuple(pred.shape) != tuple(label.shape):
+        raise ValueError(f"prediction {tuple(pred.shape)} and label {tuple(label.shape)} differ in shape")
+    label = label.to(pred.device)
+    if names is None:
+        p_thr, t_thr = 0.5, 0.0
+    else:
+        p_thr = t_thr = float(threshold)
+        if float(pred.max()) > 1.0:
+            p_thr = -math.inf if p_thr <= 0.0 else (math.inf if p_thr >= 1.0 else math.log(p_thr / (1.0 - p_thr)))
+        if float(label.max()) > 1.0:
+            t_thr = 0.0
+    state = ConfusionState(1)
+    state.update(pred[None, None], label[None, None], pred_threshold=p_thr, target_mode="threshold", target_threshold=t_thr)
+    table = state.table()
+    if names is None:
+        tn, fp, fn, tp = (int(v) for v in table[:4].tolist())
+        return {"jaccard": float(tp) / float(tp + fp + fn) if tp + fp + fn else 1.0}
+    return metrics_from_counts(table, 1, names)
+
+
 def run_test(cfg, args) -> dict:
     from .inference import InferenceManager
     from .inference.chunked import is_chunked_inference_enabled, run_chunked_prediction_inference
@@ -223,8 +255,17 @@ def run_test(cfg, args) -> dict:
     metrics = {"seconds": dt, "output_voxels_per_s": out_vox / dt}
     label_spec = cfg.data.test.label
     if label_spec and pred_t is not None:
-        lab = torch.from_numpy(np.array(read_volume(str(label_spec)), copy=True))       # an own, writable array (memmaps are read-only)
-        metrics["jaccard"] = binary_jaccard(pred_t[0, 0].float().cpu(), lab)
+        lab = np.array(read_volume(str(label_spec)), copy=True)                         # an own, writable array (memmaps are read-only)
+        if lab.dtype not in (np.uint8, np.int64, np.float32):                           # one cast to a dtype the count kernel reads
+            lab = lab.astype(np.float32 if lab.dtype.kind == "f" else np.int64)
+        ev = getattr(cfg, "evaluation", None)
+        names = list(getattr(ev, "metrics", None) or []) if ev is not None and bool(getattr(ev, "enabled", False)) else []
+        if any(n in INSTANCE_METRICS for n in names):
+            logger.warning("evaluation.metrics %s need the reference's decoding to instances: not computed here",
+                           [n for n in names if n in INSTANCE_METRICS])
+        # channel 0 of the prediction where it lies (device: the HIP count kernel; the chunked path's host array: torch on the CPU)
+        metrics.update(voxel_metrics(pred_t[0, 0], torch.from_numpy(lab), names or None,
+                                     float(getattr(ev, "prediction_threshold", 0.5)) if ev is not None else 0.5))
     (out_dir / f"{name}_metrics.json").write_text(json.dumps(metrics, indent=2))
     logger.info("test done: %s", metrics)
     return metrics

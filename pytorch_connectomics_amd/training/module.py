@@ -19,9 +19,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models import build_model
-from ..utils.channel_slices import resolve_channel_indices
-from ..utils.model_outputs import resolve_head_target_slice, unwrap_main_output
+from ..utils.channel_slices import resolve_channel_indices, resolve_channel_range
+from ..utils.model_outputs import _cfg_value as _cfg_get
+from ..utils.model_outputs import resolve_configured_output_head, resolve_head_target_slice, select_output_tensor, unwrap_main_output
 from .loss_table import loss_row
+from .metrics import ConfusionState, metrics_from_counts
 from .losses import (_mask_for_unweighted_loss, auto_pos_weight_scalar, class_balance_weight,  # noqa: F401  (re-exported: callers
                      dice_loss_sigmoid, monai_dice_loss, monai_focal_loss, monai_tversky_loss,     # and the exact-epilogue tests read
                      per_channel_bce_with_logits, weighted_bce_with_logits, weighted_regression_loss)   # them from this module)
@@ -267,6 +269,8 @@ class ConnectomicsModule(nn.Module):
         self.clamp_max = float(getattr(loss_cfg, "deep_supervision_clamp_max", 20.0))
         self.global_step = 0
         self.current_epoch = 0
+        self._val_state: Optional[ConfusionState] = None     # the validation epoch's table of counts (evaluation.enabled with metrics)
+        self.val_history: list = []                          # what fit() appends after every validate()
 
     # ---- reference-visible methods ----------------------------------------------------------------
     def forward(self, x: torch.Tensor):
@@ -547,15 +551,126 @@ class ConnectomicsModule(nn.Module):
         loss, self.last_log = self._compute_loss(outputs, batch["label"], batch.get("mask"))
         return loss
 
+    # ---- the `evaluation` block: voxel metrics of a validation epoch (training/metrics.py) ------------
+    def _evaluation_request(self):
+        """-> (the metric names `evaluation` asks for, or None when it is disabled or lists none; prediction_threshold)."""
+        ev = getattr(self.cfg, "evaluation", None)
+        names = _cfg_get(ev, "metrics", None)
+        if ev is None or not bool(_cfg_get(ev, "enabled", False)) or not names:
+            return None, 0.5
+        return [str(n) for n in names], float(_cfg_get(ev, "prediction_threshold", 0.5))
+
+    def _has_multiple_supervised_loss_tasks(self) -> bool:
+        return sum(1 for t in self.loss_terms if t["call_kind"] == "pred_target") > 1
+
+    def _validation_state(self) -> ConfusionState:
+        """The epoch's table, sized as the reference sizes its validation metrics (lightning/model.py:551-563): the selected named
+        head's width; else binary for a multi-task loss or one output channel, `model.out_channels` classes otherwise."""
+        if self._val_state is None:
+            heads = getattr(self.cfg.model, "heads", None) or {}
+            named = None
+            if heads:
+                head = resolve_configured_output_head(self.cfg, purpose="validation metric setup", allow_none=True)
+                if head is not None and head in heads:
+                    named = int(_cfg_get(heads[head], "out_channels", 0))
+            if named is not None:
+                num_classes, use_binary = named, named == 1
+            else:
+                num_classes = int(getattr(self.cfg.model, "out_channels", 2))
+                use_binary = self._has_multiple_supervised_loss_tasks() or num_classes == 1
+            self._val_state = ConfusionState(1 if use_binary else num_classes)
+        return self._val_state
+
+    def _resolve_validation_target_slice(self, head_name: str):
+        """The label slice a named head is supervised with (lightning/model.py:372-400): the head's own `target_slice`, else the one
+        target slice its pred_target loss terms agree on."""
+        explicit = resolve_head_target_slice(self.cfg, head_name)
+        if explicit is not None:
+            return explicit
+        primary = getattr(self.cfg.model, "primary_head", None)
+        matching = []
+        for t in self.loss_terms:
+            if t["call_kind"] != "pred_target":
+                continue
+            if (t["pred_head"] if t["pred_head"] is not None else primary) == head_name and t["target_slice"] not in matching:
+                matching.append(t["target_slice"])
+        if not matching:
+            raise ValueError(f"Validation metric computation could not find any pred_target loss term for head '{head_name}'.")
+        if len(matching) > 1:
+            raise ValueError(f"Validation metric computation found multiple target slices for head '{head_name}': {matching}. "
+                             "Configure a single supervised label slice for the evaluated head.")
+        return matching[0]
+
+    @staticmethod
+    def _prepare_metric_predictions(prediction: torch.Tensor, target: torch.Tensor):
+        """-> (prediction, target, target_mode) as the count kernel reads them (lightning/model.py:403-432): one output channel is
+        thresholded against a one-channel class label; several are an argmax against a class-index channel or as many one-hot channels."""
+        if int(prediction.shape[1]) == 1:
+            if int(target.shape[1]) != 1:
+                raise ValueError(f"Binary metric computation expects a single target channel, got {tuple(target.shape)}.")
+            return prediction, target, "index"
+        if int(target.shape[1]) == 1:
+            return prediction, target, "index"
+        if int(target.shape[1]) == int(prediction.shape[1]):
+            return prediction, target, "dense"
+        raise ValueError("Multiclass metric computation requires either a single class-index target channel or the same number of "
+                         f"one-hot channels as the prediction. Got prediction.shape={tuple(prediction.shape)} and "
+                         f"target.shape={tuple(target.shape)}.")
+
+    def _select_metric_operands(self, outputs, labels: torch.Tensor):
+        """The reference's choice of what a validation metric compares (lightning/model.py:935-981), as views: nothing is copied."""
+        purpose = "validation metric computation"
+        requested = resolve_configured_output_head(self.cfg, purpose=purpose, allow_none=True)
+        main, head = select_output_tensor(outputs, requested_head=requested, primary_head=getattr(self.cfg.model, "primary_head", None),
+                                          purpose=purpose)
+        if head is not None:
+            target_slice = self._resolve_validation_target_slice(head)
+            target = labels
+            if target_slice is not None:
+                a, b = resolve_channel_range(target_slice, num_channels=int(labels.shape[1]),
+                                             context=f"validation target slice for head '{head}'")
+                target = labels[:, a:b]
+            return self._prepare_metric_predictions(main, target)
+        if self._has_multiple_supervised_loss_tasks():
+            return main[:, 0:1], labels[:, 0:1], "index"          # a multi-task output: channel 0 of both, as a binary metric
+        if int(labels.shape[1]) != 1:
+            raise ValueError(f"Validation metric computation expects a single class-label channel, got {tuple(labels.shape)}.")
+        return main, labels, "index"
+
     @torch.no_grad()
     def validation_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
         outputs = self(batch["image"])
         loss, _ = self._compute_loss(outputs, batch["label"], batch.get("mask"))
-        main = unwrap_main_output(outputs)
-        p = torch.sigmoid(main[:, :1].float()) > 0.5
-        t = batch["label"][:, :1] > 0
-        union = (p | t).sum().clamp_min(1)
-        return {"val_loss_total": loss, "val_jaccard": (p & t).sum().float() / union}
+        names, threshold = self._evaluation_request()
+        if names is None:
+            main = unwrap_main_output(outputs)
+            p = torch.sigmoid(main[:, :1].float()) > 0.5
+            t = batch["label"][:, :1] > 0
+            union = (p | t).sum().clamp_min(1)
+            return {"val_loss_total": loss, "val_jaccard": (p & t).sum().float() / union}
+        # the RAW output against prediction_threshold, no sigmoid: what the reference does (lightning/model.py:416, 974-981)
+        pred, target, mode = self._select_metric_operands(outputs, batch["label"])
+        self._validation_state().update(pred, target, pred_threshold=threshold, target_mode=mode)
+        return {"val_loss_total": loss}
+
+    def validation_epoch_end(self, _riders: Optional[torch.Tensor] = None):
+        """The epoch's `val_<name>` values from the table of counts (summed over the ranks), which is then reset.  `_riders`
+        (validate()): device scalars read in the same host copy; they come back as floats, second in a tuple."""
+        names, _ = self._evaluation_request()
+        state = self._val_state
+        if names is None or state is None or state.counts is None:
+            return {} if _riders is None else ({}, [float(v) for v in _riders.reshape(-1).tolist()])
+        state.all_reduce()
+        if _riders is None:
+            out = {f"val_{k}": v for k, v in state.compute(names).items()}
+            state.reset()
+            return out
+        # counts stay exact in float64 below 2^53 voxels
+        packed = torch.cat([state.counts.to(torch.float64), _riders.detach().reshape(-1).to(state.counts.device, torch.float64)]).cpu()
+        n = state.counts.numel()
+        out = {f"val_{k}": v for k, v in metrics_from_counts(packed[:n].to(torch.int64), state.num_classes, names).items()}
+        state.reset()
+        return out, [float(v) for v in packed[n:].tolist()]
 
     def configure_optimizers(self):
         # with an adaptive loss weighter the optimizer takes the whole module (its task weights train with the network), as the
@@ -718,9 +833,41 @@ def resolve_training_steps(cfg, *, fast_dev_run: int = 0, dataset_steps_per_epoc
     return total, per_epoch
 
 
+def validate(module: ConnectomicsModule, batches, *, device, max_batches: Optional[int] = None) -> Dict[str, float]:
+    """One validation epoch over `batches` (at most `max_batches` of them) in eval mode under no_grad; the module's previous mode is
+    restored.  -> the mean of every value `validation_step` returns (`val_loss_total`; `val_jaccard` with evaluation off) plus the
+    epoch metrics of `validation_epoch_end` (`val_jaccard` / `val_dice` / `val_accuracy` with evaluation on).  Nothing is read back
+    per batch: the sums and the table of counts reach the host in one copy at the end."""
+    was_training = module.training
+    module.eval()
+    sums: Dict[str, torch.Tensor] = {}
+    n = 0
+    try:
+        with torch.no_grad():
+            for i, batch in enumerate(batches):
+                if max_batches is not None and i >= int(max_batches):
+                    break
+                batch = {k: v.to(device, non_blocking=True) for k, v in batch.items()}
+                for k, v in module.validation_step(batch, i).items():
+                    v = v.detach().to(torch.float64)
+                    sums[k] = v if k not in sums else sums[k] + v
+                n += 1
+            if n == 0:
+                raise ValueError("validate: no validation batches")
+            keys = sorted(sums)
+            metrics, host = module.validation_epoch_end(torch.stack([sums[k].reshape(()) for k in keys]))
+    finally:
+        module.train(was_training)
+    out = {k: v / n for k, v in zip(keys, host)}
+    out.update(metrics)
+    return out
+
+
 def fit(module: ConnectomicsModule, batches, *, max_steps: int, device, log_every: int = 10, ddp: bool = False,
-        log=print, steps_per_epoch: Optional[int] = None):
+        log=print, steps_per_epoch: Optional[int] = None, val_batches=None, val_every: Optional[int] = None):
     """Minimal training loop: forward (HIP) -> loss -> backward (HIP) -> clip -> optimizer (+ scheduler).
+    With `val_batches` (a re-iterable collection of batches) and `val_every`, `validate` runs every `val_every` optimizer steps and
+    after the last one; each result is logged and appended, with its step, to `module.val_history`.
     `batches` yields {"image","label"[,"mask"]} dicts of (B,C,D,H,W) tensors.  `max_steps` is the TOTAL step count of the run:
     after `load_checkpoint_dict` the loop continues from `module.global_step` with the optimizer moments, the scheduler
     position and the EMA shadow of the checkpoint.  The scheduler steps per `optimization.scheduler.interval` ('epoch', the
@@ -802,6 +949,11 @@ def fit(module: ConnectomicsModule, batches, *, max_steps: int, device, log_ever
             raise FloatingPointError(f"training loss is not finite at step {step}")
         if log and (step % log_every == 0 or step == max_steps - 1):
             log(f"step {step}: loss {history[-1]:.4f} lr {opt.param_groups[0]['lr']:.2e}")
+        if val_batches is not None and val_every and ((step + 1) % int(val_every) == 0 or step == max_steps - 1):
+            result = {"step": step + 1, **validate(module, val_batches, device=device)}
+            module.val_history.append(result)
+            if log:
+                log("validation " + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in result.items()))
     return history, opt
 
 
@@ -815,6 +967,6 @@ def synthetic_batches(batch_size: int, patch, *, in_channels=1, out_channels=1, 
         yield {"image": img, "label": lab}
 
 
-__all__ = ["ConnectomicsModule", "build_optimizer", "build_lr_scheduler", "WarmupCosineLR", "fit", "resolve_training_steps",
+__all__ = ["ConnectomicsModule", "build_optimizer", "build_lr_scheduler", "WarmupCosineLR", "fit", "validate", "resolve_training_steps",
            "match_target_to_output", "synthetic_batches",
            "dice_loss_sigmoid", "weighted_bce_with_logits", "precision_to_dtype"]
