@@ -221,7 +221,7 @@ __device__ __forceinline__ void gelu_fast_with_grad(float x, float& g, float& gd
 //     gelu(x) = max(x, 0) - r(min(|x|, U)),   r(u) = u * Phi(-u)   (a bump: 0 at 0, 0.17 at 0.75, 3.3e-4 at U = 3.75)
 // with r as a degree-7 polynomial in t = 2u/U - 1 (Chebyshev fit, |fit error| <= 1.0e-4): and, min, fma, 7 fma, max, sub =
 // 12 packed instructions per TWO elements (6 per element vs 7 VALU + 2 quarter-rate transcendentals = ~15 for gelu_fast).
-// Emulated over every fp16 input in [-8, 8]: max |error| 1.1e-3 at |x| ~ 3 (= half an fp16 ulp of the RESULT, whose
+// Emulated over every fp16 input in [-8, 8]: max |error| 1.1e-3 at |x| ~ 3.5 (= half an fp16 ulp of the RESULT, whose
 // spacing there is 2^-9; bf16, which the result used to be rounded to, has 2^-6), mean 1.5e-4.  The result IS the f16 B
 // operand of the projecting MFMA (v_mfma_f32_16x16x32_f16), so the hidden activation carries 11 mantissa bits instead of
 // bf16's 8.  Inputs are converted with round-toward-zero saturation (v_cvt_pkrtz_f16_f32: finite in, finite out).
