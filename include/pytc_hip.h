@@ -33,8 +33,10 @@ extern "C" {
  * 9: pytc_reg_* and pytc_fgcontour_* (the regularisation losses: streaming sums and gradients, the foreground / contour stencil).
  * 10: pytc_softmax_loss_* (the channel softmax reduced to eight sums per (sample, class), and its gradient: the softmax losses).
  * 11: pytc_confusion_* (logits and labels counted into a K x K table of int64: the jaccard / dice / accuracy evaluation metrics).
+ * 12: pytc_seg_erode_instance and pytc_label_targets (training targets from int32 instance labels: border erosion, affinities, binary,
+ * boundary and polarity channels with their valid mask, in one launch).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 11
+#define PYTC_ABI_VERSION 12
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1068,6 +1070,58 @@ int pytc_confusion_tiles(int64_t R);
 int pytc_confusion_counts(const float* x, const void* target, uint32_t* partial, int64_t* counts, int N, int C, int64_t R,
                           const int64_t* x_strides, const int64_t* t_strides, int target_dtype, int target_mode, float pred_threshold,
                           float target_threshold, void* stream);
+
+/* Training targets from instance labels (data/processing/segment.py:25-74, affinity.py:424-512, target.py:55-234,
+ * transforms.py:1027-1122 MultiTaskLabelTransformd).  Labels are int32 (N, D, H, W), contiguous; 0 is background, -1 the "unlabeled"
+ * sentinel.  No float touches an id: every output is exact.  D H W < 2^30.  Nothing synchronises with the host.
+ * pytc_seg_erode_instance: out[p] = seg[p] where seg[p] < 0 or the box window [p - h, p + h], h = (hz, hy, hx), clipped to the volume
+ *   (scipy's mode="reflect" adds no id a clipped window lacks) holds exactly one distinct positive id; 0 elsewhere.  Windows never
+ *   cross a sample.  out must not overlap seg (PYTC_ERR_INVALID).  0 <= h <= 10 per axis; a larger one returns PYTC_ERR_UNSUPPORTED.
+ * pytc_label_targets: one launch writes values = fp32 (N, n_channels, D, H, W) and, unless mask is null, mask of the same shape as
+ *   uint8 0 / 1 (PYTC_LABEL_MASK_U8: the storage of torch.bool) or fp32 (PYTC_LABEL_MASK_F32).  sources: n_sources <= 4 HOST pointers
+ *   to device label buffers (the patch and its eroded variants); channels: n_channels <= 32 HOST rows; both travel to the device as a
+ *   kernel argument (no allocation, no copy).  More sources or channels return PYTC_ERR_UNSUPPORTED.  values / mask must not overlap a
+ *   source or each other.  With s = the channel's source and p the output voxel:
+ *   PYTC_LABEL_AFFINITY  v[0..2] = the offset o = (dz, dy, dx), any sign and size.  deepem (default) stores the edge at its destination:
+ *     q = p - o; PYTC_LABEL_FLAG_BANIS stores it at its source: q = p + o.  q outside the volume: value 0, mask 0.  Otherwise
+ *     value = s[p] == s[q] && s[p] > 0, mask = s[p] != -1 && s[q] != -1 (o = 0: value = s[p] > 0).  PYTC_LABEL_FLAG_SEMANTIC: every
+ *     positive id reads as 1.
+ *   PYTC_LABEL_BINARY    value = s[p] > 0, or with n_ids in 1..8: s[p] is one of v[0 .. n_ids).
+ *   PYTC_LABEL_BOUNDARY  thickness 1: value = OR over the axes (z, y, x; with PYTC_LABEL_FLAG_2D: y, x) and both in-volume neighbours q of
+ *     edge(s[p], s[q]); flags & 3 = PYTC_LABEL_EDGE_ALL: a != b; _SEG_ALL: a != b && (a > 0 || b > 0); _SEG_NO_BG: a != b && a > 0 && b > 0.
+ *   PYTC_LABEL_POLARITY  flags = PYTC_LABEL_POLARITY_POS: s > 0 && s odd; _NEG: s > 0 && s even; _FG: s > 0; _EXCLUSIVE: 0 / 1 (pos) / 2 (neg).
+ *   The mask of every non-affinity channel is s[p] != -1.
+ * pytc_label_targets_tile: the voxels one workgroup covers (a pure host query; tests size their edge cases with it). */
+#define PYTC_LABEL_MAX_SOURCES 4
+#define PYTC_LABEL_MAX_CHANNELS 32
+#define PYTC_LABEL_MAX_IDS 8
+#define PYTC_LABEL_AFFINITY 0
+#define PYTC_LABEL_BINARY 1
+#define PYTC_LABEL_BOUNDARY 2
+#define PYTC_LABEL_POLARITY 3
+#define PYTC_LABEL_FLAG_BANIS 1
+#define PYTC_LABEL_FLAG_SEMANTIC 2
+#define PYTC_LABEL_EDGE_ALL 0
+#define PYTC_LABEL_EDGE_SEG_ALL 1
+#define PYTC_LABEL_EDGE_SEG_NO_BG 2
+#define PYTC_LABEL_FLAG_2D 4
+#define PYTC_LABEL_POLARITY_POS 0
+#define PYTC_LABEL_POLARITY_NEG 1
+#define PYTC_LABEL_POLARITY_FG 2
+#define PYTC_LABEL_POLARITY_EXCLUSIVE 3
+#define PYTC_LABEL_MASK_U8 0
+#define PYTC_LABEL_MASK_F32 1
+typedef struct pytc_label_channel {
+  int32_t kind;   /* PYTC_LABEL_AFFINITY ... */
+  int32_t source; /* index into sources */
+  int32_t flags;
+  int32_t n_ids;  /* PYTC_LABEL_BINARY: ids in v; 0 = every positive id */
+  int32_t v[PYTC_LABEL_MAX_IDS];
+} pytc_label_channel;
+int pytc_seg_erode_instance(const int32_t* seg, int32_t* out, int N, int D, int H, int W, int hz, int hy, int hx, void* stream);
+int pytc_label_targets_tile(void);
+int pytc_label_targets(const int32_t* const* sources, int n_sources, const pytc_label_channel* channels, int n_channels, float* values,
+                       void* mask, int mask_dtype, int N, int D, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

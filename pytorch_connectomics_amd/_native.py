@@ -11,7 +11,7 @@ import os
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libpytc_hip.so"
-ABI_VERSION = 11        # include/pytc_hip.h PYTC_ABI_VERSION
+ABI_VERSION = 12        # include/pytc_hip.h PYTC_ABI_VERSION
 
 F32, BF16 = 0, 1
 OK = 0
@@ -55,6 +55,18 @@ RAW_DTYPES = {"uint8": 0, "int8": 1, "uint16": 2, "int16": 3, "uint32": 4, "int3
 
 class ReduceItem(C.Structure):
     _fields_ = [("part", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int64), ("slots", C.c_int32), ("out_t", C.c_int32)]
+
+
+class LabelChannel(C.Structure):
+    """pytc_label_channel: one stacked target channel of pytc_label_targets."""
+    _fields_ = [("kind", C.c_int32), ("source", C.c_int32), ("flags", C.c_int32), ("n_ids", C.c_int32), ("v", C.c_int32 * 8)]
+
+
+LABEL_AFFINITY, LABEL_BINARY, LABEL_BOUNDARY, LABEL_POLARITY = 0, 1, 2, 3
+LABEL_FLAG_BANIS, LABEL_FLAG_SEMANTIC, LABEL_FLAG_2D = 1, 2, 4
+LABEL_EDGE_MODES = {"all": 0, "seg-all": 1, "seg-no-bg": 2}
+LABEL_POLARITY_POS, LABEL_POLARITY_NEG, LABEL_POLARITY_FG, LABEL_POLARITY_EXCLUSIVE = 0, 1, 2, 3
+LABEL_MAX_SOURCES, LABEL_MAX_CHANNELS, LABEL_MAX_IDS, LABEL_MAX_EROSION = 4, 32, 8, 10
 
 
 class Conv3dArgs(C.Structure):
@@ -317,6 +329,10 @@ _SIGS = {
     "pytc_confusion_tiles": (C.c_int, [C.c_int64]),
     "pytc_confusion_counts": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int64] + [C.POINTER(C.c_int64)] * 2
                               + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "pytc_seg_erode_instance": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p]),
+    "pytc_label_targets_tile": (C.c_int, []),
+    "pytc_label_targets": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(LabelChannel), C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+                           + [C.c_int] * 4 + [C.c_void_p]),
     "pytc_reg_tiles": (C.c_int, [C.c_int64]),
     "pytc_reg_pointwise_forward": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "pytc_reg_pointwise_backward": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64, C.c_float, C.c_int, C.c_void_p]),

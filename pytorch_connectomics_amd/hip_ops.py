@@ -2718,3 +2718,61 @@ def confusion_counts(x: torch.Tensor, target: torch.Tensor, counts: Optional[tor
          _CONFUSION_TARGET_DTYPES[t.dtype], CONFUSION_TARGET_MODES[target_mode], float(pred_threshold), float(target_threshold), _stream(),
          symbol="confusion_counts")
     return counts
+
+
+# ---- training targets from int32 instance labels (csrc/label_target_kernels.hip) ----
+def _label_operand(t, name: str) -> torch.Tensor:
+    _on_device(t, name)
+    if t.dtype != torch.int32 or t.dim() != 4 or t.numel() == 0 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a non-empty contiguous int32 (N, D, H, W) tensor, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def seg_erode_instance(seg: torch.Tensor, half_size: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Kisuk-Lee border erosion of int32 instance labels (N, D, H, W) (include/pytc_hip.h pytc_seg_erode_instance): a voxel keeps its id
+    where it is negative or its box window of half-size (hz, hy, hx), clipped to the volume, holds exactly one distinct positive id; it
+    becomes 0 elsewhere.  `out` must not alias `seg`."""
+    _label_operand(seg, "seg")
+    hz, hy, hx = (int(v) for v in half_size)
+    if out is None:
+        out = torch.empty_like(seg)
+    _label_operand(out, "out")
+    if out.shape != seg.shape:
+        raise ValueError(f"out must have the labels' shape {tuple(seg.shape)}, got {tuple(out.shape)}")
+    N, D, H, W = (int(v) for v in seg.shape)
+    _run(f"seg_erode_instance[{hz},{hy},{hx}]", _nbytes(seg, out), nat.lib().pytc_seg_erode_instance, _p(seg), _p(out), N, D, H, W,
+         hz, hy, hx, _stream(), symbol="seg_erode")
+    return out
+
+
+def label_targets(sources: Sequence[torch.Tensor], channels, *, mask: bool = True, mask_dtype: torch.dtype = torch.bool,
+                  values: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None):
+    """The stacked targets of int32 label buffers in one launch (include/pytc_hip.h pytc_label_targets).  sources: up to 4 int32
+    (N, D, H, W) tensors of one shape; channels: a ctypes array of `_native.LabelChannel` rows (data/label_targets.py plans it).
+    -> (values fp32 (N, C, D, H, W), mask of that shape as `mask_dtype` (torch.bool or torch.float32), or None with mask=False)."""
+    sources = list(sources)
+    if not sources:
+        raise ValueError("label_targets needs at least one source buffer")
+    for i, s in enumerate(sources):
+        _label_operand(s, f"sources[{i}]")
+        if s.shape != sources[0].shape or s.device != sources[0].device:
+            raise ValueError(f"sources[{i}] {tuple(s.shape)} on {s.device} differs from sources[0] {tuple(sources[0].shape)} on {sources[0].device}")
+    C_ = len(channels)
+    N, D, H, W = (int(v) for v in sources[0].shape)
+    if mask_dtype not in (torch.bool, torch.float32):
+        raise ValueError(f"mask_dtype must be torch.bool or torch.float32, got {mask_dtype}")
+    dev = sources[0].device
+    if values is None:
+        values = torch.empty((N, C_, D, H, W), dtype=torch.float32, device=dev)
+    _f32_operand(values, "values", shape=(N, C_, D, H, W))
+    m = None
+    if mask:
+        m = torch.empty((N, C_, D, H, W), dtype=mask_dtype, device=dev) if mask_out is None else mask_out
+        if not m.is_cuda or m.dtype != mask_dtype or tuple(m.shape) != (N, C_, D, H, W) or not m.is_contiguous():
+            raise ValueError(f"mask_out must be a contiguous {mask_dtype} CUDA(HIP) tensor of shape {(N, C_, D, H, W)}")
+    ptrs = (C.c_void_p * len(sources))(*[s.data_ptr() for s in sources])
+    V = D * H * W
+    _run(f"label_targets[C={C_}]", 4 * N * V * len(sources) + 4 * N * C_ * V + (0 if m is None else m.element_size() * N * C_ * V),
+         nat.lib().pytc_label_targets, ptrs, len(sources), channels, C_, _p(values), _p(m), 1 if mask_dtype == torch.float32 else 0,
+         N, D, H, W, _stream(), symbol="label_targets")
+    return values, m

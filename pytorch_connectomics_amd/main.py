@@ -271,10 +271,74 @@ def run_test(cfg, args) -> dict:
     return metrics
 
 
+def _label_targets_of(cfg):
+    """`data.label_transform` when it names targets (the device transform builds them from instance ids), else None."""
+    lt = getattr(getattr(cfg, "data", None), "label_transform", None)
+    targets = getattr(lt, "targets", None) if lt is not None else None
+    return lt if targets is not None and len(targets) > 0 else None
+
+
+def train_batches(cfg, module, dev, *, rank: int = 0, demo: bool = False):
+    """The endless batch iterator of `run_train`: synthetic (random://) batches, or patches sampled from .npy volumes.  With a real
+    label volume and non-empty `data.label_transform.targets` the label stays an integer volume (range-checked to int32, never a
+    float), the sampler yields id patches and the device transform (data/label_targets.py) turns each batch into the stacked targets
+    and their `label_mask`; every other configuration feeds `label > 0` or the class numbers as before."""
+    from .training import synthetic_batches
+    patch = tuple(cfg.data.dataloader.patch_size or cfg.model.input_size or (64, 64, 64))
+    bs = int(cfg.data.dataloader.batch_size)
+    img_spec = cfg.data.train.image
+    if img_spec is None or str(img_spec).startswith("random://") or demo:
+        return synthetic_batches(bs, patch, in_channels=cfg.model.in_channels, out_channels=cfg.model.out_channels,
+                                 seed=int(cfg.system.seed) + rank, device=dev)
+    from .utils.volume_normalize import normalize_image_for_config
+    vol = torch.from_numpy(np.ascontiguousarray(normalize_image_for_config(read_volume(str(img_spec)), cfg), dtype=np.float32))
+    g = torch.Generator().manual_seed(int(cfg.system.seed) + rank)
+    label_cfg = _label_targets_of(cfg)
+    plan = None
+    if label_cfg is not None:
+        from .data import LabelTargetTransform, device_target_batches, labels_to_int32
+        plan = LabelTargetTransform.from_config(label_cfg)
+        sliced = any(t.get("target_slice") is not None or t.get("pred_slice") is not None for t in module.loss_terms)
+        if not sliced and not getattr(cfg.model, "heads", None) and plan.channels != int(cfg.model.out_channels):
+            raise ValueError(f"data.label_transform.targets stack {plan.channels} channels ({', '.join(plan.channel_names)}) but "
+                             f"model.out_channels is {int(cfg.model.out_channels)} and no loss term names a pred_slice / target_slice")
+        lab = torch.from_numpy(np.array(labels_to_int32(np.asarray(read_volume(str(cfg.data.train.label))), "data.train.label"),
+                                        dtype=np.int32, copy=True))
+        if tuple(lab.shape) != tuple(vol.shape):
+            raise ValueError(f"data.train.label {tuple(lab.shape)} and data.train.image {tuple(vol.shape)} differ in shape")
+    else:
+        lab = torch.from_numpy(np.ascontiguousarray(read_volume(str(cfg.data.train.label))).astype(np.float32))
+    # a class-index term (CrossEntropyLoss, or to_onehot_y of the softmax losses) reads the label volume's class numbers; every
+    # other configuration keeps the binary foreground target
+    keep_classes = any(t.get("target_kind") == "class_index" or bool(t["kwargs"].get("to_onehot_y", False)) for t in module.loss_terms)
+
+    def sampler():
+        while True:
+            xs, ys = [], []
+            for _ in range(bs):
+                # a 2-D patch_size on a 3-D volume = one z-slice per sample (data.*.do_2d semantics)
+                full = ((1,) * (vol.dim() - len(patch))) + tuple(patch)
+                o = [int(torch.randint(0, vol.shape[a] - full[a] + 1, (1,), generator=g)) for a in range(vol.dim())]
+                sl = tuple(slice(o[a], o[a] + full[a]) for a in range(vol.dim()))
+                xv, yv = vol[sl].reshape(patch), lab[sl].reshape(patch)
+                xs.append(xv[None])
+                if plan is not None:
+                    ys.append(yv if len(patch) == 3 else yv[None])           # ids: (D, H, W), a 2-D patch as one plane
+                else:
+                    ys.append((yv if keep_classes else (yv > 0).float())[None])
+            yield {"image": torch.stack(xs), "label": torch.stack(ys)}
+    if plan is None:
+        return sampler()
+    batches = device_target_batches(sampler(), plan, dev, mask_dtype=torch.float32)
+    if len(patch) == 3:
+        return batches
+    return ({k: (v.squeeze(2) if k in ("label", "label_mask") else v) for k, v in b.items()} for b in batches)
+
+
 def run_train(cfg, args) -> dict:
     """DDP-ready training loop on synthetic (random://) patches or patches sampled from .npy volumes."""
     import os
-    from .training import ConnectomicsModule, fit, synthetic_batches
+    from .training import ConnectomicsModule, fit
     if not torch.cuda.is_available():
         raise RuntimeError("train mode needs an MI355X (ROCm) device: this engine has no CPU path")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -295,31 +359,7 @@ def run_train(cfg, args) -> dict:
     steps, per_epoch = resolve_training_steps(cfg, fast_dev_run=int(args.fast_dev_run or 0))
     if args.fast_dev_run and args.checkpoint:
         steps += int(module.global_step)          # --fast-dev-run N on a resumed run = N MORE steps (Lightning runs N batches)
-    img_spec = cfg.data.train.image
-    if img_spec is None or str(img_spec).startswith("random://") or args.demo:
-        batches = synthetic_batches(bs, patch, in_channels=cfg.model.in_channels, out_channels=cfg.model.out_channels,
-                                    seed=int(cfg.system.seed) + rank, device=dev)
-    else:
-        from .utils.volume_normalize import normalize_image_for_config
-        vol = torch.from_numpy(np.ascontiguousarray(normalize_image_for_config(read_volume(str(img_spec)), cfg), dtype=np.float32))
-        lab = torch.from_numpy(np.ascontiguousarray(read_volume(str(cfg.data.train.label))).astype(np.float32))
-        g = torch.Generator().manual_seed(int(cfg.system.seed) + rank)
-        # a class-index term (CrossEntropyLoss, or to_onehot_y of the softmax losses) reads the label volume's class numbers; every
-        # other configuration keeps the binary foreground target
-        keep_classes = any(t.get("target_kind") == "class_index" or bool(t["kwargs"].get("to_onehot_y", False)) for t in module.loss_terms)
-
-        def sampler():
-            while True:
-                xs, ys = [], []
-                for _ in range(bs):
-                    # a 2-D patch_size on a 3-D volume = one z-slice per sample (data.*.do_2d semantics)
-                    full = ((1,) * (vol.dim() - len(patch))) + tuple(patch)
-                    o = [int(torch.randint(0, vol.shape[a] - full[a] + 1, (1,), generator=g)) for a in range(vol.dim())]
-                    sl = tuple(slice(o[a], o[a] + full[a]) for a in range(vol.dim()))
-                    xv, yv = vol[sl].reshape(patch), lab[sl].reshape(patch)
-                    xs.append(xv[None]); ys.append((yv if keep_classes else (yv > 0).float())[None])
-                yield {"image": torch.stack(xs), "label": torch.stack(ys)}
-        batches = sampler()
+    batches = train_batches(cfg, module, dev, rank=rank, demo=bool(args.demo))
     t0 = time.perf_counter()
     history, opt = fit(module, batches, max_steps=steps, device=dev, ddp=world > 1, log=logger.info if rank == 0 else None,
                        steps_per_epoch=per_epoch)

@@ -60,6 +60,26 @@ def resize_class_index_to_output(t: torch.Tensor, output: torch.Tensor) -> torch
     return r.to(t.dtype) if t.dtype.is_floating_point else r.long()
 
 
+def check_label_mask(label_mask: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The per-channel valid mask the label transform emits, as the float factor the loss terms multiply (orchestrator.py:484-498):
+    bool, or the device transform's fp32 0 / 1 form, of the labels' shape."""
+    if label_mask.dtype not in (torch.bool, torch.float32):
+        raise TypeError(f"label_mask must have dtype torch.bool, got {label_mask.dtype}")
+    if label_mask.shape[:2] != labels.shape[:2] or label_mask.shape[2:] != labels.shape[2:]:
+        raise ValueError("label_mask must have the same batch, channel, and spatial shape as labels: "
+                         f"label_mask={tuple(label_mask.shape)}, labels={tuple(labels.shape)}")
+    return label_mask if label_mask.dtype == torch.float32 else label_mask.to(torch.float32)
+
+
+def resize_label_mask_to_output(label_mask: torch.Tensor, output: torch.Tensor) -> torch.Tensor:
+    """A (float 0 / 1) label mask at a deep-supervision output's resolution (orchestrator.py:405-422): the invalid voxels are
+    area-averaged, and a coarse voxel is valid only if no fine voxel under it is invalid."""
+    if label_mask.shape[2:] == output.shape[2:]:
+        return label_mask
+    invalid = F.interpolate(1.0 - label_mask, size=output.shape[2:], mode="area")
+    return (invalid <= 0.0).to(label_mask.dtype)
+
+
 class WarmupCosineLR(torch.optim.lr_scheduler.LRScheduler):
     """lr = eta_min + (base * warmup(t) - eta_min) * 0.5 (1 + cos(pi t / max_iters))."""
 
@@ -291,7 +311,13 @@ class ConnectomicsModule(nn.Module):
         return bool(kw.get("sigmoid", False)) and smooth_ok and bg_ok and not kw.get("squared_pred", False) and \
             not (set(kw) - {"sigmoid", "smooth_nr", "smooth_dr", "include_background", "squared_pred"})
 
-    def _fused_term_loss(self, pred, target, mask, terms):
+    def _term_label_mask(self, t, label_mask):
+        """The channels of the label mask a term's targets come from: its `target_slice`, or all of them."""
+        if t["target_slice"] is None:
+            return label_mask
+        return label_mask[:, resolve_channel_indices(t["target_slice"], num_channels=label_mask.shape[1], context="target_slice")]
+
+    def _fused_term_loss(self, pred, target, mask, terms, label_mask=None):
         """All terms are BCE-with-logits / sigmoid-Dice: one fused HIP reduction per (pred_slice, target_slice) pair."""
         from .fused import bce_dice_loss
         groups = {}
@@ -313,7 +339,13 @@ class ConnectomicsModule(nn.Module):
             wb = g["bce"][1]["weight"] if g["bce"] else 0.0
             wd = g["dice"][1]["weight"] if g["dice"] else 0.0
             pw = g["bce"][1]["pos_weight"] if g["bce"] else None        # (None for a loss without a weight map: plan_loss_terms)
-            v, out = bce_dice_loss(p, y, mask, w_bce=wb, w_dice=wd, pos_weight=pw)
+            m = mask
+            if label_mask is not None:
+                # the term's channels of the label mask join the batch mask; the kernel reads the product as its per-channel weight
+                lm = self._term_label_mask(t, label_mask)
+                y = torch.where(lm > 0, y, torch.zeros_like(y))
+                m = lm if mask is None else mask * lm
+            v, out = bce_dice_loss(p, y, m, w_bce=wb, w_dice=wd, pos_weight=pw)
             if g["bce"]:
                 parts[f"loss_{g['bce'][0]}_{g['bce'][1]['fn']}"] = out[1]
             if g["dice"]:
@@ -327,13 +359,15 @@ class ConnectomicsModule(nn.Module):
         plain_bce_masked = mask is not None and any(t["row"].fused == "bce" and t["row"].spatial is None for _, t in terms)
         return bool(pred.is_cuda and self.fused_loss and not plain_bce_masked and all(self._term_is_fusable(t, pred) for _, t in terms))
 
-    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None, full_labels=None):
+    def _term_loss(self, pred, target, mask=None, terms=None, tasks=None, heads=None, full_labels=None, label_mask=None):
         """Weighted sum of the loss terms `terms` (list of (index, term); default: all) on one prediction tensor.
         tasks: a dict that receives {term index: static weight x raw value, WITH its graph} (adaptive balancing: the caller
         combines the tasks); the fused kernel steps aside then -- it returns one scalar for all its terms.
         heads: the named-head outputs, for a `pred_pred` term whose second slice comes from another head.
         full_labels: on a deep-supervision scale, the labels at full resolution: a `class_index` term (CrossEntropyLoss) resizes ITS
-        channel of them by nearest neighbour (orchestrator.py:277-291, 578-586) instead of reading the densely resized `target`."""
+        channel of them by nearest neighbour (orchestrator.py:277-291, 578-586) instead of reading the densely resized `target`.
+        label_mask: the label transform's per-channel valid mask (float 0 / 1, at this scale): every supervised term multiplies its
+        `target_slice` channels of it into its valid mask; None takes the path without one, unchanged."""
         terms = list(enumerate(self.loss_terms)) if terms is None else terms
         pred = torch.clamp(pred, min=self.clamp_min, max=self.clamp_max)
         total, parts = 0.0, {}
@@ -342,15 +376,15 @@ class ConnectomicsModule(nn.Module):
             # it: those are judged on their own, the rest is added below
             # (nor do the softmax losses and L1Loss, which have kernels or rows of their own)
             supervised = [(i, t) for i, t in terms if not t["row"].beside_fused]
-            if supervised and self._fusable(pred, mask, supervised):
-                res = self._fused_term_loss(pred, target, mask, supervised)      # finiteness is checked where fit() reads the value
+            if supervised and self._fusable(pred, mask if mask is not None else label_mask, supervised):
+                res = self._fused_term_loss(pred, target, mask, supervised, label_mask)   # finiteness is checked where fit() reads the value
                 if res is not None:
                     if len(supervised) == len(terms):
                         return res
                     total, parts = res
                     terms = [(i, t) for i, t in terms if t["row"].beside_fused]
         for i, t in terms:
-            v = self._supervised_loss(i, t, pred, target, mask, full_labels) if t["row"].call == "pred_target" else \
+            v = self._supervised_loss(i, t, pred, target, mask, full_labels, label_mask) if t["row"].call == "pred_target" else \
                 self._regularizer_loss(i, t, pred, target, mask, heads)
             if not torch.isfinite(v):
                 raise FloatingPointError(f"loss term {t['fn']} is not finite")
@@ -360,7 +394,7 @@ class ConnectomicsModule(nn.Module):
             total = total + t["weight"] * v
         return total, parts
 
-    def _supervised_loss(self, i, t, pred, target, mask, full_labels):
+    def _supervised_loss(self, i, t, pred, target, mask, full_labels, label_mask=None):
         """A `pred_target` term on the clamped predictions: its slices, its target form and its spatial argument."""
         row = t["row"]
         p, y = pred, target
@@ -375,6 +409,12 @@ class ConnectomicsModule(nn.Module):
                 raise ValueError(f"Loss term 'loss_{i}_{t['fn']}' takes a class-index target of one channel, got "
                                  f"{tuple(y.shape)} (name it with target_slice)")
             y = resize_class_index_to_output(y, pred)
+        if label_mask is not None:
+            # the transform's valid mask of the term's target channels (orchestrator.py:492-498, 635-648): a factor of everything
+            # the batch mask is a factor of, and invalid targets read as 0
+            lm = self._term_label_mask(t, label_mask)
+            y = torch.where(lm > 0, y, torch.zeros_like(y))
+            mask = lm if mask is None else mask * lm
         # what the loss sees as its spatial argument (reference orchestrator.py:566-646): a term's own mask channels
         # (`mask_slice` of the labels) x the batch mask; a `weight`-taking loss without a mask of its own gets the
         # class-balancing map instead (unless its pos_weight is a scalar of its own)
@@ -422,7 +462,7 @@ class ConnectomicsModule(nn.Module):
             v = t["loss"](*args)
         return v
 
-    def _balanced_scale_loss(self, items, stage: str, heads=None, full_labels=None):
+    def _balanced_scale_loss(self, items, stage: str, heads=None, full_labels=None, label_mask=None):
         """One output scale under adaptive loss balancing (orchestrator.py:110-127, 779-790): `items` = [(pred, target, mask, terms)]
         (one entry per head); every term is a task whose loss is its static weight x raw value, the weighter combines ALL tasks of
         the scale in one call.  Uncertainty weighting on fusable terms keeps the fused HIP loss: the per-task coefficients
@@ -437,7 +477,8 @@ class ConnectomicsModule(nn.Module):
                              f"carries terms {idx} (apply_deep_supervision: false on a term is not compatible with loss_balancing)")
         names = [f"loss_{i}_{self.loss_terms[i]['fn']}" for i in idx]
         parts: Dict[str, Any] = {}
-        if isinstance(w, UncertaintyLossWeighter) and all(self._fusable(torch.clamp(p, self.clamp_min, self.clamp_max), m, terms)
+        if isinstance(w, UncertaintyLossWeighter) and all(self._fusable(torch.clamp(p, self.clamp_min, self.clamp_max),
+                                                                        m if m is not None else label_mask, terms)
                                                            for p, _, m, terms in items):
             coef = 0.5 * torch.exp(-w.log_vars)
             host = [float(c) for c in coef.detach().cpu().tolist()]
@@ -445,7 +486,7 @@ class ConnectomicsModule(nn.Module):
             raw: Dict[int, torch.Tensor] = {}
             for pred, target, mask, terms in items:
                 scaled = [(i, {**t, "weight": t["weight"] * host[i]}) for i, t in terms]
-                res = self._fused_term_loss(torch.clamp(pred, min=self.clamp_min, max=self.clamp_max), target, mask, scaled)
+                res = self._fused_term_loss(torch.clamp(pred, min=self.clamp_min, max=self.clamp_max), target, mask, scaled, label_mask)
                 if res is None:
                     ok = False
                     break
@@ -465,7 +506,7 @@ class ConnectomicsModule(nn.Module):
             parts = {}
         tasks: Dict[int, torch.Tensor] = {}
         for pred, target, mask, terms in items:
-            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks, heads=heads, full_labels=full_labels)
+            _, pr = self._term_loss(pred, target, mask, terms, tasks=tasks, heads=heads, full_labels=full_labels, label_mask=label_mask)
             parts.update(pr)
         total, wts, logs = w.combine([tasks[i] for i in idx], names, stage)
         for n, wt in zip(names, wts):
@@ -493,8 +534,10 @@ class ConnectomicsModule(nn.Module):
             raise TypeError(f"Output head '{want}' must be a tensor, got {type(heads[want]).__name__}.")
         return want
 
-    def _compute_loss(self, outputs, labels, mask=None):
+    def _compute_loss(self, outputs, labels, mask=None, label_mask=None):
         stage = "train" if self.training else "val"
+        if label_mask is not None:
+            label_mask = check_label_mask(label_mask, labels)
         main = unwrap_main_output(outputs)
         if isinstance(main, dict):
             # named heads: every term reads its own head; the terms of one head share a (fused) reduction
@@ -506,10 +549,10 @@ class ConnectomicsModule(nn.Module):
             total, parts = 0.0, {}
             if self.loss_weighter is not None:
                 total, parts = self._balanced_scale_loss([(main[head], labels, mask, terms) for head, terms in by_head.items()], stage,
-                                                         heads=main)
+                                                         heads=main, label_mask=label_mask)
             else:
                 for head, terms in by_head.items():
-                    v, pr = self._term_loss(main[head], labels, mask, terms, heads=main)
+                    v, pr = self._term_loss(main[head], labels, mask, terms, heads=main, label_mask=label_mask)
                     total = total + v
                     parts.update(pr)
             total = self.ds_weights[0] * total
@@ -524,9 +567,9 @@ class ConnectomicsModule(nn.Module):
                                  "output is a single tensor.")
         all_terms = list(enumerate(self.loss_terms))
         if self.loss_weighter is not None:
-            total, parts = self._balanced_scale_loss([(main, labels, mask, all_terms)], stage)
+            total, parts = self._balanced_scale_loss([(main, labels, mask, all_terms)], stage, label_mask=label_mask)
         else:
-            total, parts = self._term_loss(main, labels, mask)
+            total, parts = self._term_loss(main, labels, mask, label_mask=label_mask)
         total = self.ds_weights[0] * total
         if self.deep_supervision and isinstance(outputs, dict):
             for i in range(1, 5):
@@ -535,20 +578,21 @@ class ConnectomicsModule(nn.Module):
                     continue
                 tgt = match_target_to_output(labels, ds)
                 m = None if mask is None else resize_class_index_to_output(mask, ds)
+                lm = None if label_mask is None else resize_label_mask_to_output(label_mask, ds)
                 on_scales = [(j, t) for j, t in enumerate(self.loss_terms) if t.get("apply_deep_supervision", True)]
                 if not on_scales:
                     continue
                 if self.loss_weighter is not None:
-                    li, _ = self._balanced_scale_loss([(ds, tgt, m, on_scales)], stage, full_labels=labels)
+                    li, _ = self._balanced_scale_loss([(ds, tgt, m, on_scales)], stage, full_labels=labels, label_mask=lm)
                 else:
-                    li, _ = self._term_loss(ds, tgt, m, on_scales, full_labels=labels)
+                    li, _ = self._term_loss(ds, tgt, m, on_scales, full_labels=labels, label_mask=lm)
                 total = total + self.ds_weights[i] * li
         parts["train_loss_total"] = total.detach()
         return total, parts
 
     def training_step(self, batch: Dict[str, torch.Tensor], batch_idx: int = 0) -> torch.Tensor:
         outputs = self(batch["image"])
-        loss, self.last_log = self._compute_loss(outputs, batch["label"], batch.get("mask"))
+        loss, self.last_log = self._compute_loss(outputs, batch["label"], batch.get("mask"), batch.get("label_mask"))
         return loss
 
     # ---- the `evaluation` block: voxel metrics of a validation epoch (training/metrics.py) ------------
@@ -640,7 +684,7 @@ class ConnectomicsModule(nn.Module):
     @torch.no_grad()
     def validation_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
         outputs = self(batch["image"])
-        loss, _ = self._compute_loss(outputs, batch["label"], batch.get("mask"))
+        loss, _ = self._compute_loss(outputs, batch["label"], batch.get("mask"), batch.get("label_mask"))
         names, threshold = self._evaluation_request()
         if names is None:
             main = unwrap_main_output(outputs)
@@ -868,7 +912,7 @@ def fit(module: ConnectomicsModule, batches, *, max_steps: int, device, log_ever
     """Minimal training loop: forward (HIP) -> loss -> backward (HIP) -> clip -> optimizer (+ scheduler).
     With `val_batches` (a re-iterable collection of batches) and `val_every`, `validate` runs every `val_every` optimizer steps and
     after the last one; each result is logged and appended, with its step, to `module.val_history`.
-    `batches` yields {"image","label"[,"mask"]} dicts of (B,C,D,H,W) tensors.  `max_steps` is the TOTAL step count of the run:
+    `batches` yields {"image","label"[,"mask"][,"label_mask"]} dicts of (B,C,D,H,W) tensors.  `max_steps` is the TOTAL step count of the run:
     after `load_checkpoint_dict` the loop continues from `module.global_step` with the optimizer moments, the scheduler
     position and the EMA shadow of the checkpoint.  The scheduler steps per `optimization.scheduler.interval` ('epoch', the
     reference default, every `steps_per_epoch` optimizer steps; or 'step') and `frequency` (lightning/model.py:1174-1200)."""
@@ -914,7 +958,7 @@ def fit(module: ConnectomicsModule, batches, *, max_steps: int, device, log_ever
         for _ in range(accum):
             batch = {k: v.to(device, non_blocking=True) for k, v in next(it).items()}
             out = net(batch["image"])
-            loss, logs = module._compute_loss(out, batch["label"], batch.get("mask"))
+            loss, logs = module._compute_loss(out, batch["label"], batch.get("mask"), batch.get("label_mask"))
             (loss / accum).backward()
         if weighter_params:
             world = torch.distributed.get_world_size()
@@ -968,5 +1012,5 @@ def synthetic_batches(batch_size: int, patch, *, in_channels=1, out_channels=1, 
 
 
 __all__ = ["ConnectomicsModule", "build_optimizer", "build_lr_scheduler", "WarmupCosineLR", "fit", "validate", "resolve_training_steps",
-           "match_target_to_output", "synthetic_batches",
+           "match_target_to_output", "synthetic_batches", "check_label_mask", "resize_label_mask_to_output",
            "dice_loss_sigmoid", "weighted_bce_with_logits", "precision_to_dtype"]
