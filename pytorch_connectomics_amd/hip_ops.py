@@ -1607,8 +1607,9 @@ def copy_zero_front(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-_ST_CODES = {"uint8": (0, torch.uint8), "int8": (1, torch.int8), "uint16": (2, torch.uint16), "int16": (3, torch.int16),
-             "int32": (4, torch.int32), "float16": (5, torch.float16), "float32": (6, torch.float32)}
+_ST_CODES = {"uint8": (nat.ST_U8, torch.uint8), "int8": (nat.ST_I8, torch.int8), "uint16": (nat.ST_U16, torch.uint16),
+             "int16": (nat.ST_I16, torch.int16), "int32": (nat.ST_I32, torch.int32), "float16": (nat.ST_F16, torch.float16),
+             "float32": (nat.ST_F32, torch.float32)}
 
 
 def scale_cast(x: torch.Tensor, *, scale: float = 1.0, target: str = "float32") -> torch.Tensor:
@@ -2459,7 +2460,7 @@ def scnp_logits(x: torch.Tensor, t: torch.Tensor, ns: int) -> torch.Tensor:
 
 
 # ---- regularisation losses: streaming sums / gradients and the foreground-contour stencil (csrc/regularization_kernels.hip) ---------
-REG_KINDS = {"binary": 0, "fg_dist": 1, "ct_dist": 2, "nonoverlap": 3}
+REG_KINDS = {"binary": nat.REG_BINARY, "fg_dist": nat.REG_FG_DIST, "ct_dist": nat.REG_CT_DIST, "nonoverlap": nat.REG_NONOVERLAP}
 
 
 def _reg_geo(kind: str, a: torch.Tensor, b: Optional[torch.Tensor], mask: Optional[torch.Tensor]):
@@ -2667,8 +2668,8 @@ def softmax_loss_backward(gsums: torch.Tensor, x: torch.Tensor, target: torch.Te
 
 # ---- evaluation metrics: logits and labels counted into a K x K table of int64 (csrc/metric_kernels.hip) ----
 CONFUSION_MAX_C = 32
-CONFUSION_TARGET_MODES = {"index": 0, "threshold": 1, "dense": 2}
-_CONFUSION_TARGET_DTYPES = {torch.float32: 0, torch.int64: 1, torch.uint8: 2}
+CONFUSION_TARGET_MODES = {"index": nat.CONFUSION_INDEX, "threshold": nat.CONFUSION_THRESHOLD, "dense": nat.CONFUSION_DENSE}
+_CONFUSION_TARGET_DTYPES = {torch.float32: nat.TARGET_F32, torch.int64: nat.TARGET_I64, torch.uint8: nat.TARGET_U8}
 
 
 def confusion_counts(x: torch.Tensor, target: torch.Tensor, counts: Optional[torch.Tensor] = None, *, target_mode: str = "index",
@@ -2773,6 +2774,6 @@ def label_targets(sources: Sequence[torch.Tensor], channels, *, mask: bool = Tru
     ptrs = (C.c_void_p * len(sources))(*[s.data_ptr() for s in sources])
     V = D * H * W
     _run(f"label_targets[C={C_}]", 4 * N * V * len(sources) + 4 * N * C_ * V + (0 if m is None else m.element_size() * N * C_ * V),
-         nat.lib().pytc_label_targets, ptrs, len(sources), channels, C_, _p(values), _p(m), 1 if mask_dtype == torch.float32 else 0,
-         N, D, H, W, _stream(), symbol="label_targets")
+         nat.lib().pytc_label_targets, ptrs, len(sources), channels, C_, _p(values), _p(m),
+         nat.LABEL_MASK_F32 if mask_dtype == torch.float32 else nat.LABEL_MASK_U8, N, D, H, W, _stream(), symbol="label_targets")
     return values, m

@@ -25,9 +25,110 @@ def test_library_exports_every_declared_symbol():
     handle = ctypes.CDLL(str(_native.LIB_PATH))
     for name in declared:
         assert hasattr(handle, name), f"{name} declared in pytc_hip.h but not exported"
-    assert set(_native.exported_symbols()) <= set(declared)
+    assert set(_native.exported_symbols()) == set(declared)
     header = (ROOT / "include" / "pytc_hip.h").read_text()
     assert lib.pytc_abi_version() == _native.ABI_VERSION == int(re.search(r"#define PYTC_ABI_VERSION (\d+)", header).group(1))
+
+
+def test_derived_signatures_of_the_prototypes_a_reader_could_misread():
+    """The binding is derived from include/pytc_hip.h (_native.parse_header); these are the prototypes where a regular-expression reader
+    slips first, written out by hand from the header: a `const char*` return, `(void)`, an int64_t return, a double, a float among ints,
+    struct pointers, a pointer to const pointers, a `char*` buffer with `int*` out-parameters, a host `float*`, 24 parameters."""
+    from pytorch_connectomics_amd import _native as nat
+    i, i64, f, d, vp, s = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
+    expected = {
+        "pytc_last_error": (s, []),
+        "pytc_label_targets_tile": (i, []),
+        "pytc_window_normalize_ws_elems": (i64, [i, i64]),
+        "pytc_fgcontour_forward": (i, [vp] * 6 + [i] * 4 + [d, vp]),
+        "pytc_gather_windows": (i, [vp, i, i, i, i, vp, i, i, i, i, i, i, f, vp, i, vp]),
+        "pytc_pw_conv_fwd": (i, [ctypes.POINTER(nat.PwArgs), vp]),
+        "pytc_label_targets": (i, [vp, i, ctypes.POINTER(nat.LabelChannel), i, vp, vp, i, i, i, i, i, vp]),
+        "pytc_device_info": (i, [i, vp, vp, s, i]),
+        "pytc_adamw_multi": (i, [vp, vp, i, vp, i, vp, vp]),
+        "pytc_mixer_bwd_rc": (i, [vp] * 9 + [f] + [vp] * 4 + [i] * 3 + [i64] + [i] * 4 + [vp, vp]),
+    }
+    assert len(expected["pytc_mixer_bwd_rc"][1]) == 24
+    lib = nat.lib()
+    for name, (res, args) in expected.items():
+        assert nat.SIGNATURES[name] == (res, args), name
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    # the status codes are published (INTEGRATION.md); the tests compare against these names
+    assert (nat.OK, nat.ERR_INVALID, nat.ERR_HIP, nat.ERR_UNSUPPORTED) == (0, 1, 2, 3)
+
+
+def test_struct_layouts_equal_the_compilers(tmp_path):
+    """sizeof and every offsetof of the five argument structs, as the host C compiler lays the header out, against the ctypes classes
+    derived from the same header."""
+    import shutil
+    import subprocess
+    from pytorch_connectomics_amd import _native as nat
+    cc = shutil.which("cc")
+    if cc is None:
+        pytest.skip("no host C compiler (cc) on PATH")
+    assert sorted(nat.STRUCTS) == ["pytc_conv3d_args", "pytc_label_channel", "pytc_mlp_args", "pytc_pw_args", "pytc_reduce_item"]
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "pytc_hip.h"', 'int main(void) {']
+    for cname, cls in nat.STRUCTS.items():
+        lines.append(f'  printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'  printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));' for field, _ in cls._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}", ""]))
+    subprocess.run([cc, "-std=c99", f"-I{ROOT / 'include'}", str(src), "-o", str(tmp_path / "layout")], check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    compiled = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    derived = {}
+    for cname, cls in nat.STRUCTS.items():
+        derived[cname] = ctypes.sizeof(cls)
+        derived.update({f"{cname}.{field}": getattr(cls, field).offset for field, _ in cls._fields_})
+    assert compiled == derived and len(derived) == 5 + 73
+    assert nat.LabelChannel is nat.STRUCTS["pytc_label_channel"] and ctypes.sizeof(nat.LabelChannel) == 4 * (4 + nat.LABEL_MAX_IDS)
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int pytc_f(uint96_t n);", "pytc_f.*uint96_t"),                                                    # an unknown parameter type
+    ("typedef struct { int n; } pytc_s;\nint pytc_f(pytc_s a);", "pytc_f.*pytc_s.*by value"),           # a struct by value
+    ("#define PYTC_X (1 << 3)\nint pytc_f(void);", "PYTC_X"),                                           # a define that is no literal
+    ("#define PYTC_X 1.5\nint pytc_f(void);", "PYTC_X"),
+    ("#define LEN pytc_foo(3)\nint pytc_f(void);", r"pytc_foo"),                                        # a pytc_foo( outside a prototype
+    ("void pytc_foo(int n);", "pytc_foo"),                                                              # ... and a return type not read
+    ("typedef struct { int32_t v[N_IDS]; } pytc_s;\nint pytc_f(void);", "pytc_s.*N_IDS"),               # an array bound of neither kind
+    ("typedef struct { int32_t v[PYTC_N]; } pytc_s;\nint pytc_f(void);", "pytc_s.*PYTC_N"),
+    ("int pytc_f(int (*callback)(int));", "pytc_f"),                                                    # a function pointer
+    ("int pytc_f(const char* fmt, ...);", "pytc_f"),                                                    # variadic
+    ("int pytc_f(unsigned int n);", "pytc_f.*unsigned"),
+    ("int pytc_f(int n);\nint pytc_f(int n);", "pytc_f.*twice"),
+])
+def test_header_reader_refuses_what_it_does_not_read(text, names):
+    """The reader reads include/pytc_hip.h, not C: what it would have to guess at raises, naming the item, so that a prototype it
+    skipped can never become a function bound without argument types."""
+    from pytorch_connectomics_amd import _native as nat
+    with pytest.raises(ValueError, match=names):
+        nat.parse_header(text)
+
+
+def test_header_reader_on_a_small_header():
+    from pytorch_connectomics_amd import _native as nat
+    consts, structs, sigs = nat.parse_header("""
+        #ifndef PYTC_HIP_H
+        #define PYTC_HIP_H
+        #include <stdint.h>
+        extern "C" {
+        #define PYTC_N 3   /* a comment with pytc_ghost( in it */
+        #define PYTC_MASK 0x10  // and another: pytc_ghost2(
+        typedef struct tag { const float* p; int a, b; double d; int32_t v[PYTC_N]; int64_t w[2]; } pytc_s;
+        const char * pytc_name ( void ) ;
+        int64_t pytc_g(const pytc_s* s, const int32_t* const* pp, pytc_s** out, char* buf, const char* key, float x, int32_t);
+        }
+        #endif
+        """)
+    assert consts == {"N": 3, "MASK": 16}
+    assert [(n, t) for n, t in structs["pytc_s"]._fields_] == [("p", ctypes.c_void_p), ("a", ctypes.c_int), ("b", ctypes.c_int),
+                                                              ("d", ctypes.c_double), ("v", ctypes.c_int32 * 3), ("w", ctypes.c_int64 * 2)]
+    vp = ctypes.c_void_p
+    assert sigs == {"pytc_name": (ctypes.c_char_p, []),
+                    "pytc_g": (ctypes.c_int64, [ctypes.POINTER(structs["pytc_s"]), vp, vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_float,
+                                                ctypes.c_int32])}
 
 
 def test_abi_pure_host_queries():
@@ -93,7 +194,6 @@ def test_tuning_knob_registry_is_closed():
     any other key -- a retired knob, a typo -- is refused with PYTC_ERR_INVALID and named in the last-error string."""
     from pytorch_connectomics_amd import _native as nat
     lib = nat.lib()
-    ERR_INVALID = 1        # PYTC_ERR_INVALID
     table = (ROOT / "pytorch_connectomics_amd" / "csrc" / "pytc_common.h").read_text()
     rows = re.findall(r"^\s*X\((\w+), ([^,]+), \"[^\"]+\"\)", table, flags=re.M)
     assert rows and len(rows) == table.count("\n  X(") and len({k for k, _ in rows}) == len(rows) and "dwconv_mfma" in dict(rows), rows
@@ -104,9 +204,9 @@ def test_tuning_knob_registry_is_closed():
         finally:
             assert lib.pytc_set_tuning(key.encode(), default) == nat.OK, key
     for key in ("mlp_exact_gelu", "dwconv_mfma_probe", "dwconv_mfmma", ""):
-        assert lib.pytc_set_tuning(key.encode(), 1) == ERR_INVALID, key
+        assert lib.pytc_set_tuning(key.encode(), 1) == nat.ERR_INVALID, key
         assert key in lib.pytc_last_error().decode()
-    assert lib.pytc_set_tuning(None, 1) == ERR_INVALID
+    assert lib.pytc_set_tuning(None, 1) == nat.ERR_INVALID
 
 
 def test_depthwise_dispatch_table_and_batch_invariant_statistics_slots():

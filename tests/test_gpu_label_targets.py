@@ -135,7 +135,7 @@ def test_refusals():
     out = torch.empty_like(seg)
     st = ops._stream()
     p = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
-    INVALID, UNSUPPORTED = 1, 3
+    INVALID, UNSUPPORTED = nat.ERR_INVALID, nat.ERR_UNSUPPORTED
     # aliasing `out` (the same buffer, and one overlapping it), a null pointer, a half-size of 11
     assert lib.pytc_seg_erode_instance(p(seg), p(seg), 1, 2, 8, 8, 0, 1, 1, st) == INVALID and b"alias" in lib.pytc_last_error()
     both = torch.zeros((2 * seg.numel() - 4,), dtype=torch.int32, device="cuda")

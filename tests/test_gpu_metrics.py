@@ -176,8 +176,8 @@ def test_refusals_on_the_device():
     z = torch.zeros(64, device="cuda")
     s3 = (C.c_int64 * 3)(8, 8, 1)
     p = lambda t: C.c_void_p(t.data_ptr())                                                            # noqa: E731
-    assert nat.lib().pytc_confusion_counts(p(z), p(z), p(z), p(z), 1, 33, 1, s3, s3, 0, 0, 0.5, 0.5, None) == 3      # UNSUPPORTED
-    assert nat.lib().pytc_confusion_counts(p(z), p(z), p(z), p(z), 1, 2, 1, s3, s3, 0, 1, 0.5, 0.5, None) == 1       # INVALID
+    assert nat.lib().pytc_confusion_counts(p(z), p(z), p(z), p(z), 1, 33, 1, s3, s3, 0, 0, 0.5, 0.5, None) == nat.ERR_UNSUPPORTED
+    assert nat.lib().pytc_confusion_counts(p(z), p(z), p(z), p(z), 1, 2, 1, s3, s3, 0, 1, 0.5, 0.5, None) == nat.ERR_INVALID
 
 
 # ---- module, profiler, CLI -----------------------------------------------------------------------------------------------------
