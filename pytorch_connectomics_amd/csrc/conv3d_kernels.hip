@@ -282,21 +282,22 @@ static int conv_c1_stencil_oct(bool has_pre, bool has_res, int Do, int Ho, int W
   return C_out >= 32 ? 32 : (C_out >= 8 ? 8 : (C_out > 1 ? 4 : 1));
 }
 
-// -> true when the launch was made (conv_c1_stencil_oct)
-bool conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const float* ab, int act_in, const EpiParams& e, int N,
-                         int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
-                         int dtype, hipStream_t s) {
+// -> *launched: the launch was made (conv_c1_stencil_oct); the status is that of the dtype dispatch
+int conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const float* ab, int act_in, const EpiParams& e, int N,
+                        int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
+                        int dtype, hipStream_t s, bool* launched) {
   const int oct = conv_c1_stencil_oct(ab != nullptr || act_in != PYTC_ACT_NONE, e.res_mode != PYTC_RES_NONE, Do, Ho, Wo, Di, Hi, Wi, C_in,
                                       C_out, kd, kh, kw, stride, pad);
-  if (!oct) return false;
+  *launched = oct != 0;
+  if (!oct) return PYTC_OK;
   const long total = (long)N * Do * Ho * Wo;
   dim3 grid((unsigned)((total + 255) / 256), (unsigned)((C_out + oct - 1) / oct));
-#define PYTC_C1(TT, OCTV) hipLaunchKernelGGL((conv3d_c1_stencil_kernel<TT, OCTV>), grid, dim3(256), 0, s, (const TT*)x, (const TT*)wp, bias, \
-                                             (TT*)e.y, N, Do, Ho, Wo, Di, Hi, Wi, C_out, stride)
-  if (dtype == PYTC_BF16) { if (oct == 32) PYTC_C1(bf16_t, 32); else if (oct == 8) PYTC_C1(bf16_t, 8); else if (oct == 4) PYTC_C1(bf16_t, 4); else PYTC_C1(bf16_t, 1); }
-  else { if (oct == 32) PYTC_C1(float, 32); else if (oct == 8) PYTC_C1(float, 8); else if (oct == 4) PYTC_C1(float, 4); else PYTC_C1(float, 1); }
+#define PYTC_C1(OCTV) hipLaunchKernelGGL((conv3d_c1_stencil_kernel<T, OCTV>), grid, dim3(256), 0, s, (const T*)x, (const T*)wp, bias, \
+                                         (T*)e.y, N, Do, Ho, Wo, Di, Hi, Wi, C_out, stride)
+  PYTC_DISPATCH_DTYPE(dtype, "conv3d", T,
+                      if (oct == 32) PYTC_C1(32); else if (oct == 8) PYTC_C1(8); else if (oct == 4) PYTC_C1(4); else PYTC_C1(1));
 #undef PYTC_C1
-  return true;
+  return PYTC_OK;
 }
 
 // ---- LDS-tiled form (bf16, C_in % 8 == 0) ------------------------------------------------------------------------------
@@ -835,11 +836,9 @@ static void launch_conv(const ConvParams& p, hipStream_t s) {
 
 using namespace pytc;
 
-static int kstep_of(int dtype) { return dtype == PYTC_BF16 ? 32 : 16; }
-
 extern "C" int64_t pytc_conv3d_packed_elems(int C_out, int C_in, int kd, int kh, int kw, int dtype) {
   if (C_out < 1 || C_in < 1 || kd < 1 || kh < 1 || kw < 1 || (dtype != PYTC_F32 && dtype != PYTC_BF16)) return -1;
-  int ks = kstep_of(dtype);
+  int ks = mfma_kstep(dtype);
   const int64_t direct = (int64_t)((C_out + 15) / 16) * 16 * kd * kh * kw * ((C_in + ks - 1) / ks) * ks;
   ConvTile t; size_t lds_bytes;
   if (!conv_tile_plan(dtype, C_in, kd, kh, kw, t, lds_bytes)) return direct;
@@ -851,21 +850,20 @@ extern "C" int64_t pytc_conv3d_packed_elems(int C_out, int C_in, int kd, int kh,
 static int pack_conv_weight(const float* w, int C_out, int C_in, int kd, int kh, int kw, void* packed, int dtype, long s_o,
                             long s_c, int flip, void* stream) {
   PYTC_REQUIRE(w && packed, "conv3d_pack_weight: null pointer");
+  PYTC_CHECK_DTYPE(dtype, "conv3d_pack_weight");
   long total = pytc_conv3d_packed_elems(C_out, C_in, kd, kh, kw, dtype);
   PYTC_REQUIRE(total > 0, "conv3d_pack_weight: bad arguments");
-  int KG = (C_in + kstep_of(dtype) - 1) / kstep_of(dtype);
+  int KG = (C_in + mfma_kstep(dtype) - 1) / mfma_kstep(dtype);
   dim3 grid(ceil_div(total, 256)), block(256);
   ConvTile t; size_t lds_bytes;
   if (conv_tile_plan(dtype, C_in, kd, kh, kw, t, lds_bytes)) {      // the LDS-tiled kernel's layout (same rule as the launch)
     const long tot2 = (long)((C_out + 15) / 16) * t.nchunks * t.G * 64 * 8;
     hipLaunchKernelGGL(conv3d_pack_flat_kernel, dim3(ceil_div(tot2, 256)), block, 0, (hipStream_t)stream, w, C_out, C_in,
                        kd * kh * kw, (bf16_t*)packed, t.KC, t.nchunks, t.G, tot2, s_o, s_c, flip);
-  } else if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(conv3d_pack_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
-                       (bf16_t*)packed, KG, total, s_o, s_c, flip);
-  else
-    hipLaunchKernelGGL(conv3d_pack_kernel<float>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
-                       (float*)packed, KG, total, s_o, s_c, flip);
+  } else
+    PYTC_DISPATCH_DTYPE(dtype, "conv3d_pack_weight", T,
+                        hipLaunchKernelGGL(conv3d_pack_kernel<T>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
+                                           (T*)packed, KG, total, s_o, s_c, flip));
   PYTC_LAUNCH_CHECK("conv3d_pack_weight");
   return PYTC_OK;
 }
@@ -890,7 +888,7 @@ extern "C" int pytc_conv3d_pack_weight_dgrad(const float* w, int C_out, int C_in
 extern "C" int pytc_conv3d_pack_plan(int C_out, int C_in, int kd, int kh, int kw, int dtype, int direct, int64_t* out) {
   PYTC_REQUIRE(out && C_out >= 1 && C_in >= 1 && kd >= 1 && kh >= 1 && kw >= 1 && (dtype == PYTC_F32 || dtype == PYTC_BF16),
                "conv3d_pack_plan: bad arguments");
-  const int ks = kstep_of(dtype);
+  const int ks = mfma_kstep(dtype);
   ConvTile t; size_t lds_bytes;
   if (!direct && conv_tile_plan(dtype, C_in, kd, kh, kw, t, lds_bytes)) {
     out[0] = 1; out[1] = t.KC; out[2] = t.nchunks; out[3] = t.G;
@@ -924,12 +922,12 @@ extern "C" int pytc_conv3d_fwd(const pytc_conv3d_args* a, void* stream) {
   PYTC_REQUIRE(a && a->x && a->w_packed && a->y, "conv3d: null pointer");
   PYTC_REQUIRE(a->N >= 1 && a->D >= 1 && a->H >= 1 && a->W >= 1 && a->C_in >= 1 && a->C_out >= 1, "conv3d: bad shape");
   PYTC_REQUIRE((a->kd & 1) && (a->kh & 1) && (a->kw & 1), "conv3d: kernel sizes must be odd ('same' padding)");
-  PYTC_REQUIRE(a->dtype == PYTC_F32 || a->dtype == PYTC_BF16, "conv3d: bad dtype");
+  PYTC_CHECK_DTYPE(a->dtype, "conv3d");
   PYTC_REQUIRE(a->res_mode == PYTC_RES_NONE || (a->res_mode == PYTC_RES_ADD && a->res), "conv3d: bad residual");
   ConvParams p;
   p.x = a->x; p.wp = a->w_packed; p.bias = a->bias; p.ab = a->ab;
   p.N = a->N; p.D = a->D; p.H = a->H; p.W = a->W; p.C_in = a->C_in; p.C_out = a->C_out;
-  p.KG = (a->C_in + kstep_of(a->dtype) - 1) / kstep_of(a->dtype);
+  p.KG = (a->C_in + mfma_kstep(a->dtype) - 1) / mfma_kstep(a->dtype);
   p.MTt = (a->C_out + 15) / 16;
   p.kd = a->kd; p.kh = a->kh; p.kw = a->kw;
   p.act_in = a->act_in; p.act_param = a->act_param; p.act_out = PYTC_ACT_NONE;
@@ -940,16 +938,17 @@ extern "C" int pytc_conv3d_fwd(const pytc_conv3d_args* a, void* stream) {
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   hipStream_t s = (hipStream_t)stream;
   ConvTile t; size_t lds_bytes;
+  bool stencil;
   switch (conv_fwd_form(a->dtype, a->ab != nullptr || a->act_in != PYTC_ACT_NONE, a->res_mode != PYTC_RES_NONE, a->D, a->H, a->W, a->C_in,
                         a->C_out, a->kd, a->kh, a->kw, t, lds_bytes)) {
     case CONV_FORM_STENCIL:
-      conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, a->D, a->H, a->W, a->C_in, a->C_out,
-                          a->kd, a->kh, a->kw, 1, 1, a->dtype, s);
+      if (int st = conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, a->D, a->H, a->W, a->C_in,
+                                       a->C_out, a->kd, a->kh, a->kw, 1, 1, a->dtype, s, &stencil))
+        return st;
       break;
     case CONV_FORM_TILE: launch_conv_tile(p, t, lds_bytes, s); break;
     default:                                                 // (launch_conv picks the thin-input or the MFMA gather kernel)
-      if (a->dtype == PYTC_F32) launch_conv<float, float, float>(p, s);
-      else launch_conv<bf16_t, bf16_t, bf16_t>(p, s);
+      PYTC_DISPATCH_DTYPE(a->dtype, "conv3d", T, launch_conv<T, T, T>(p, s));
   }
   PYTC_LAUNCH_CHECK("conv3d");
   return PYTC_OK;

@@ -14,9 +14,9 @@
 namespace pytc {
 
 // conv3d_kernels.hip: the scalar-field stencil for one input channel (3^3 taps, stride 1 / 2)
-bool conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const float* ab, int act_in, const EpiParams& e, int N,
-                         int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
-                         int dtype, hipStream_t s);
+int conv_c1_stencil_try(const void* x, const void* wp, const float* bias, const float* ab, int act_in, const EpiParams& e, int N,
+                        int Do, int Ho, int Wo, int Di, int Hi, int Wi, int C_in, int C_out, int kd, int kh, int kw, int stride, int pad,
+                        int dtype, hipStream_t s, bool* launched);
 
 struct SConvParams {
   const void* x;
@@ -835,27 +835,23 @@ static bool sw_c1_line_ok(const SwGeom& g, int C_k, int C_o, int dtype) {
   return (size_t)(9 * (g.Wb + 2) + g.Ws * C_o) * sizeof(float) <= 64 * 1024 && 2 * (g.Ws - 1) + 2 - 1 < g.Wb + 1;
 }
 
-static int s_kstep(int dtype) { return dtype == PYTC_BF16 ? 32 : 16; }
-
 extern "C" int64_t pytc_conv3d_direct_packed_elems(int C_out, int C_in, int kd, int kh, int kw, int dtype) {
   if (C_out < 1 || C_in < 1 || kd < 1 || kh < 1 || kw < 1 || (dtype != PYTC_F32 && dtype != PYTC_BF16)) return -1;
-  const int ks = s_kstep(dtype);
+  const int ks = mfma_kstep(dtype);
   return (int64_t)((C_out + 15) / 16) * 16 * kd * kh * kw * ((C_in + ks - 1) / ks) * ks;
 }
 
 extern "C" int pytc_conv3d_pack_weight_direct(const float* w, int C_out, int C_in, int kd, int kh, int kw, int64_t s_o,
                                               int64_t s_c, int flip, void* packed, int dtype, void* stream) {
   PYTC_REQUIRE(w && packed, "conv3d_pack_weight_direct: null pointer");
+  PYTC_CHECK_DTYPE(dtype, "conv3d_pack_weight_direct");
   const long total = pytc_conv3d_direct_packed_elems(C_out, C_in, kd, kh, kw, dtype);
   PYTC_REQUIRE(total > 0, "conv3d_pack_weight_direct: bad arguments");
-  const int KG = (C_in + s_kstep(dtype) - 1) / s_kstep(dtype);
+  const int KG = (C_in + mfma_kstep(dtype) - 1) / mfma_kstep(dtype);
   dim3 grid(ceil_div(total, 256)), block(256);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(conv3d_pack_direct_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
-                       (bf16_t*)packed, KG, total, (long)s_o, (long)s_c, flip);
-  else
-    hipLaunchKernelGGL(conv3d_pack_direct_kernel<float>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
-                       (float*)packed, KG, total, (long)s_o, (long)s_c, flip);
+  PYTC_DISPATCH_DTYPE(dtype, "conv3d_pack_weight_direct", T,
+                      hipLaunchKernelGGL(conv3d_pack_direct_kernel<T>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, kd * kh * kw,
+                                         (T*)packed, KG, total, (long)s_o, (long)s_c, flip));
   PYTC_LAUNCH_CHECK("conv3d_pack_weight_direct");
   return PYTC_OK;
 }
@@ -866,13 +862,13 @@ extern "C" int pytc_conv3d_strided_fwd(const pytc_conv3d_args* a, const int32_t*
   PYTC_REQUIRE(a->N >= 1 && a->D >= 1 && a->H >= 1 && a->W >= 1 && a->C_in >= 1 && a->C_out >= 1, "conv3d_strided: bad shape");
   PYTC_REQUIRE(in_dims[0] >= 1 && in_dims[1] >= 1 && in_dims[2] >= 1 && stride[0] >= 1 && stride[1] >= 1 && stride[2] >= 1 &&
                pad[0] >= 0 && pad[1] >= 0 && pad[2] >= 0, "conv3d_strided: bad geometry");
-  PYTC_REQUIRE(a->dtype == PYTC_F32 || a->dtype == PYTC_BF16, "conv3d_strided: bad dtype");
+  PYTC_CHECK_DTYPE(a->dtype, "conv3d_strided");
   PYTC_REQUIRE(a->res_mode == PYTC_RES_NONE || (a->res_mode == PYTC_RES_ADD && a->res), "conv3d_strided: bad residual");
   SConvParams p;
   p.x = a->x; p.wp = a->w_packed; p.bias = a->bias; p.ab = a->ab;
   p.N = a->N; p.Do = a->D; p.Ho = a->H; p.Wo = a->W; p.C_in = a->C_in; p.C_out = a->C_out;
   p.Di = in_dims[0]; p.Hi = in_dims[1]; p.Wi = in_dims[2];
-  p.KG = (a->C_in + s_kstep(a->dtype) - 1) / s_kstep(a->dtype);
+  p.KG = (a->C_in + mfma_kstep(a->dtype) - 1) / mfma_kstep(a->dtype);
   p.MTt = (a->C_out + 15) / 16;
   p.kd = a->kd; p.kh = a->kh; p.kw = a->kw;
   p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
@@ -884,11 +880,12 @@ extern "C" int pytc_conv3d_strided_fwd(const pytc_conv3d_args* a, const int32_t*
   p.e.rps_out = (long)a->D * a->H * a->W; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode; p.e.nt = 0;
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   hipStream_t s = (hipStream_t)stream;
-  if (!transposed && stride[0] == stride[1] && stride[1] == stride[2] && pad[0] == pad[1] && pad[1] == pad[2] &&
-      conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, p.Di, p.Hi, p.Wi, a->C_in, a->C_out,
-                          a->kd, a->kh, a->kw, stride[0], pad[0], a->dtype, s)) {}
-  else if (a->dtype == PYTC_F32) launch_sconv<float, float, float>(p, s);
-  else launch_sconv<bf16_t, bf16_t, bf16_t>(p, s);
+  bool stencil = false;
+  if (!transposed && stride[0] == stride[1] && stride[1] == stride[2] && pad[0] == pad[1] && pad[1] == pad[2])
+    if (int st = conv_c1_stencil_try(a->x, a->w_packed, a->bias, a->ab, a->act_in, p.e, a->N, a->D, a->H, a->W, p.Di, p.Hi, p.Wi, a->C_in,
+                                     a->C_out, a->kd, a->kh, a->kw, stride[0], pad[0], a->dtype, s, &stencil))
+      return st;
+  if (!stencil) PYTC_DISPATCH_DTYPE(a->dtype, "conv3d_strided", T, launch_sconv<T, T, T>(p, s));
   PYTC_LAUNCH_CHECK("conv3d_strided");
   return PYTC_OK;
 }
@@ -929,44 +926,32 @@ extern "C" int pytc_conv3d_wgrad_strided(const void* big, const void* small, flo
     else if (mp.nt == 2) SW_MFMA(1, 2);
     else SW_MFMA(1, 1);
 #undef SW_MFMA
-  } else if (sw_c1_line_ok(g, C_k, C_o, dtype)) {
-    // slot = a run of whole x-lines; the workspace query (pytc_conv3d_wgrad_strided_ws_elems) sizes for sw_slots(): never more here
-    const long lines_total = (long)N * g.Ds * g.Hs;
-    int lslots = (int)(lines_total < slots ? lines_total : slots);
-    const int lps = (int)((lines_total + lslots - 1) / lslots);
-    lslots = (int)((lines_total + lps - 1) / lps);
-    slots = lslots;
-    const size_t lds = (size_t)(9 * (g.Wb + 2) + g.Ws * C_o) * sizeof(float);
-#define SW_C1(TT, COGV) hipLaunchKernelGGL((conv3d_wgrad_s2_c1_line_kernel<TT, COGV>), dim3((unsigned)lslots), block, lds, s, (const TT*)big, \
-                                           (const TT*)small, workspace, N, g, C_o, lps)
-    if (dtype == PYTC_BF16) { if (C_o == 32) SW_C1(bf16_t, 1); else SW_C1(bf16_t, 2); }
-    else { if (C_o == 32) SW_C1(float, 1); else SW_C1(float, 2); }
+  } else {
+#define SW_C1(COGV) hipLaunchKernelGGL((conv3d_wgrad_s2_c1_line_kernel<T, COGV>), dim3((unsigned)lslots), block, lds, s, (const T*)big, \
+                                       (const T*)small, workspace, N, g, C_o, lps)
+    PYTC_DISPATCH_DTYPE(dtype, "conv3d_wgrad_strided", T,
+      if (sw_c1_line_ok(g, C_k, C_o, dtype)) {
+        // slot = a run of whole x-lines; the workspace query (pytc_conv3d_wgrad_strided_ws_elems) sizes for sw_slots(): never more here
+        const long lines_total = (long)N * g.Ds * g.Hs;
+        int lslots = (int)(lines_total < slots ? lines_total : slots);
+        const int lps = (int)((lines_total + lslots - 1) / lslots);
+        lslots = (int)((lines_total + lps - 1) / lps);
+        slots = lslots;
+        const size_t lds = (size_t)(9 * (g.Wb + 2) + g.Ws * C_o) * sizeof(float);
+        if (C_o == 32) SW_C1(1); else SW_C1(2);
+      } else if (C_k == 1 && g.kd == 3 && g.kh == 3 && g.kw == 3) {
+        dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO);
+        hipLaunchKernelGGL(conv3d_wgrad_strided_thin1_kernel<T>, tgrid, block, 0, s, (const T*)big, (const T*)small, workspace, rows_total,
+                           g, C_o, rps, slots);
+      } else if (C_k <= SWT_KMAX) {
+        dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO, taps);
+        hipLaunchKernelGGL(conv3d_wgrad_strided_thin_kernel<T>, tgrid, block, 0, s, (const T*)big, (const T*)small, workspace, rows_total,
+                           g, C_k, C_o, rps, slots);
+      } else {
+        hipLaunchKernelGGL(conv3d_wgrad_strided_kernel<T>, grid, block, 0, s, (const T*)big, (const T*)small, workspace, rows_total, g, C_k,
+                           C_o, rps, slots);
+      });
 #undef SW_C1
-  } else if (C_k == 1 && g.kd == 3 && g.kh == 3 && g.kw == 3 && (dtype == PYTC_BF16 || dtype == PYTC_F32)) {
-    dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO);
-    if (dtype == PYTC_BF16)
-      hipLaunchKernelGGL(conv3d_wgrad_strided_thin1_kernel<bf16_t>, tgrid, block, 0, s, (const bf16_t*)big, (const bf16_t*)small,
-                         workspace, rows_total, g, C_o, rps, slots);
-    else
-      hipLaunchKernelGGL(conv3d_wgrad_strided_thin1_kernel<float>, tgrid, block, 0, s, (const float*)big, (const float*)small,
-                         workspace, rows_total, g, C_o, rps, slots);
-  } else if (C_k <= SWT_KMAX && (dtype == PYTC_BF16 || dtype == PYTC_F32)) {
-    dim3 tgrid(slots, (C_o + SWT_TO - 1) / SWT_TO, taps);
-    if (dtype == PYTC_BF16)
-      hipLaunchKernelGGL(conv3d_wgrad_strided_thin_kernel<bf16_t>, tgrid, block, 0, s, (const bf16_t*)big, (const bf16_t*)small,
-                         workspace, rows_total, g, C_k, C_o, rps, slots);
-    else
-      hipLaunchKernelGGL(conv3d_wgrad_strided_thin_kernel<float>, tgrid, block, 0, s, (const float*)big, (const float*)small,
-                         workspace, rows_total, g, C_k, C_o, rps, slots);
-  } else if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(conv3d_wgrad_strided_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)big, (const bf16_t*)small,
-                       workspace, rows_total, g, C_k, C_o, rps, slots);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(conv3d_wgrad_strided_kernel<float>, grid, block, 0, s, (const float*)big, (const float*)small,
-                       workspace, rows_total, g, C_k, C_o, rps, slots);
-  else {
-    set_error("conv3d_wgrad_strided: bad dtype %d", dtype);
-    return PYTC_ERR_INVALID;
   }
   const long nW = (long)taps * C_o * C_k;
   hipLaunchKernelGGL(sw_reduce_slots_kernel, dim3(ceil_div(nW, 16)), dim3(256), 0, s, workspace, dW, nW, slots);
@@ -983,17 +968,10 @@ extern "C" int pytc_convT3d_c1_fwd(const void* x, const float* w, const float* b
   const long total = rows * 8;
   const size_t lds = (size_t)27 * C_in * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) {
-    hipLaunchKernelGGL(convT3d_c1_dots_kernel<bf16_t>, dim3((unsigned)((rows + 255) / 256)), dim3(256), lds, s, (const bf16_t*)x, w, workspace, rows, C_in);
-    hipLaunchKernelGGL(convT3d_c1_gather_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, workspace, bias, (bf16_t*)y, N,
-                       in_dims[0], in_dims[1], in_dims[2]);
-  } else if (dtype == PYTC_F32) {
-    hipLaunchKernelGGL(convT3d_c1_dots_kernel<float>, dim3((unsigned)((rows + 255) / 256)), dim3(256), lds, s, (const float*)x, w, workspace, rows, C_in);
-    hipLaunchKernelGGL(convT3d_c1_gather_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, workspace, bias, (float*)y, N,
-                       in_dims[0], in_dims[1], in_dims[2]);
-  } else {
-    PYTC_REQUIRE(false, "convT3d_c1: bad dtype %d", dtype);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "convT3d_c1", T,
+    hipLaunchKernelGGL(convT3d_c1_dots_kernel<T>, dim3((unsigned)((rows + 255) / 256)), dim3(256), lds, s, (const T*)x, w, workspace, rows, C_in);
+    hipLaunchKernelGGL(convT3d_c1_gather_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, workspace, bias, (T*)y, N,
+                       in_dims[0], in_dims[1], in_dims[2]));
   PYTC_LAUNCH_CHECK("convT3d_c1");
   return PYTC_OK;
 }
@@ -1011,14 +989,9 @@ extern "C" int pytc_convT3d_thin_fwd(const void* x, const float* w, const float*
   if (blocks > 65536) blocks = 65536;
   const size_t lds = (size_t)27 * C_out * C_in * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(convT3d_thin_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, s, (const bf16_t*)x, w, bias, (bf16_t*)y, N,
-                       in_dims[0], in_dims[1], in_dims[2], C_in, C_out);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(convT3d_thin_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, s, (const float*)x, w, bias, (float*)y, N,
-                       in_dims[0], in_dims[1], in_dims[2], C_in, C_out);
-  else
-    PYTC_REQUIRE(false, "convT3d_thin: bad dtype %d", dtype);
+  PYTC_DISPATCH_DTYPE(dtype, "convT3d_thin", T,
+                      hipLaunchKernelGGL(convT3d_thin_kernel<T>, dim3((unsigned)blocks), dim3(256), lds, s, (const T*)x, w, bias, (T*)y, N,
+                                         in_dims[0], in_dims[1], in_dims[2], C_in, C_out));
   PYTC_LAUNCH_CHECK("convT3d_thin");
   return PYTC_OK;
 }

@@ -1123,15 +1123,14 @@ int dw_wgrad_march_slots(int N, int D, int H, int W, int C, int K, int stride, i
   return t.slots * N;
 }
 
-void dw_wgrad_march_launch(const void* gr, const void* x, float* dWp, float* dbp, int N, int D, int H, int W, int C,
-                           int dtype, hipStream_t s) {
+int dw_wgrad_march_launch(const void* gr, const void* x, float* dWp, float* dbp, int N, int D, int H, int W, int C,
+                          int dtype, hipStream_t s) {
   DwMarch t;
   make_wgrad_march(t, N, D, H, W, C);
   dim3 grid((unsigned)((long)t.slots * (C / MARCH_CG) * N)), block(256);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(dw_wgrad_march_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)gr, (const bf16_t*)x, dWp, dbp, t);
-  else
-    hipLaunchKernelGGL(dw_wgrad_march_kernel<float>, grid, block, 0, s, (const float*)gr, (const float*)x, dWp, dbp, t);
+  PYTC_DISPATCH_DTYPE(dtype, "dw_wgrad", T,
+                      hipLaunchKernelGGL(dw_wgrad_march_kernel<T>, grid, block, 0, s, (const T*)gr, (const T*)x, dWp, dbp, t));
+  return PYTC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1186,7 +1185,7 @@ groupnorm_finalize_kernel(const float* __restrict__ stats, int slots, float coun
 }
 
 static int pick_vec(int C, int dtype) {
-  int maxv = dtype == PYTC_BF16 ? 8 : 4;
+  int maxv = elems_per_16b(dtype);
   for (int v = maxv; v > 1; v >>= 1)
     if (C % v == 0 && (C / v) <= 256) return v;
   return C <= 256 ? 1 : 0;
@@ -1285,7 +1284,7 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
   }
   PYTC_REQUIRE(N >= 1 && D >= 1 && H >= 1 && W >= 1 && C >= 1, "dwconv3d: bad shape");
   PYTC_REQUIRE(stride == 1 || stride == 2, "dwconv3d: stride must be 1 or 2");
-  PYTC_REQUIRE(dtype == PYTC_F32 || dtype == PYTC_BF16, "dwconv3d: bad dtype");
+  PYTC_CHECK_DTYPE(dtype, "dwconv3d");
   PYTC_REQUIRE(!(wide_range && stats), "dwconv3d_fwd_wide: the gradient entry computes no statistics");
   // the up blocks' resampling conv at C = 64 / 128: one tile of input cells per workgroup (dwconvT_tile_kernels.hip).  The plan is made
   // FIRST: a shape it rejects falls through to the generic kernels, which take a null output only in their cell form (checked below)
@@ -1375,9 +1374,8 @@ static int dw_entry(bool transposed, const void* x, void* y, const float* w, con
     return PYTC_ERR_UNSUPPORTED;
   }
   PYTC_REQUIRE((size_t)g.vs * 2 * C * sizeof(float) <= 64 * 1024, "dwconv3d: stats scratch too large");
-  int rc = dtype == PYTC_BF16 ? dispatch_vec<bf16_t>(vec, transposed, x, y, w, bias, stats, g, (hipStream_t)stream)
-                              : dispatch_vec<float>(vec, transposed, x, y, w, bias, stats, g, (hipStream_t)stream);
-  if (rc != PYTC_OK) return rc;
+  PYTC_DISPATCH_DTYPE(dtype, "dwconv3d", T,
+                      if (int rc = dispatch_vec<T>(vec, transposed, x, y, w, bias, stats, g, (hipStream_t)stream)) return rc);
   PYTC_LAUNCH_CHECK("dwconv3d");
   return PYTC_OK;
 }

@@ -298,28 +298,20 @@ extern "C" int pytc_affine_act(const void* x, void* y, const float* ab, int N, i
                                int dtype, void* stream) {
   PYTC_REQUIRE(x && y && N >= 1 && rows >= 1 && C >= 1, "affine_act: bad arguments");
   const long total = (long)N * rows * C;
-  const int vec = dtype == PYTC_BF16 ? 8 : 4;
-  if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
+  const int vec = elems_per_16b(dtype);
+  if (C % vec == 0 && tuning_get(K_elementwise_vec)) {
     const long chunks = total / vec;
     const int vb = (int)((chunks + 255) / 256 < 16384 ? (chunks + 255) / 256 : 16384);
-    if (dtype == PYTC_BF16)
-      hipLaunchKernelGGL(affine_act_vec_kernel<bf16_t>, dim3(vb), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, ab,
-                         (long)rows, C, act, prm, chunks);
-    else
-      hipLaunchKernelGGL(affine_act_vec_kernel<float>, dim3(vb), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, ab,
-                         (long)rows, C, act, prm, chunks);
+    PYTC_DISPATCH_DTYPE(dtype, "affine_act", T,
+                        hipLaunchKernelGGL(affine_act_vec_kernel<T>, dim3(vb), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, ab,
+                                           (long)rows, C, act, prm, chunks));
     PYTC_LAUNCH_CHECK("affine_act");
     return PYTC_OK;
   }
   int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(affine_act_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, ab, (long)rows, C, act, prm, total);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(affine_act_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       (float*)y, ab, (long)rows, C, act, prm, total);
-  else
-    PYTC_REQUIRE(false, "affine_act: bad dtype");
+  PYTC_DISPATCH_DTYPE(dtype, "affine_act", T,
+                      hipLaunchKernelGGL(affine_act_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, ab,
+                                         (long)rows, C, act, prm, total));
   PYTC_LAUNCH_CHECK("affine_act");
   return PYTC_OK;
 }
@@ -333,20 +325,12 @@ extern "C" int pytc_channel_stats(const void* x, float* stats, int N, int64_t ro
   const int Cw = C < 256 ? C : 256;
   size_t lds = (size_t)(256 / Cw) * 2 * Cw * sizeof(float);
   dim3 grid(slots, N), block(256);
-  if (dtype == PYTC_BF16 && C % 8 == 0)
-    hipLaunchKernelGGL((colstats_kernel<bf16_t, 0>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)nullptr,
-                       (const float*)nullptr, stats, (long)rows, C, slots, rps);
-  else if (dtype == PYTC_F32 && C % 4 == 0)
-    hipLaunchKernelGGL((colstats_kernel<float, 0>), grid, block, 0, (hipStream_t)stream, (const float*)x, (const float*)nullptr,
-                       (const float*)nullptr, stats, (long)rows, C, slots, rps);
-  else if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(channel_stats_kernel<bf16_t>, grid, block, lds, (hipStream_t)stream, (const bf16_t*)x, stats,
-                       (long)rows, C, slots, rps);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(channel_stats_kernel<float>, grid, block, lds, (hipStream_t)stream, (const float*)x, stats,
-                       (long)rows, C, slots, rps);
-  else
-    PYTC_REQUIRE(false, "channel_stats: bad dtype");
+  PYTC_DISPATCH_DTYPE(dtype, "channel_stats", T,
+    if (C % elems_per_16b_of<T> == 0)
+      hipLaunchKernelGGL((colstats_kernel<T, 0>), grid, block, 0, (hipStream_t)stream, (const T*)x, (const T*)nullptr,
+                         (const float*)nullptr, stats, (long)rows, C, slots, rps);
+    else
+      hipLaunchKernelGGL(channel_stats_kernel<T>, grid, block, lds, (hipStream_t)stream, (const T*)x, stats, (long)rows, C, slots, rps));
   PYTC_LAUNCH_CHECK("channel_stats");
   return PYTC_OK;
 }
@@ -387,14 +371,9 @@ extern "C" int pytc_maxpool3d_fwd(const void* x, void* y, int N, int D, int H, i
   PYTC_REQUIRE(Do >= 1 && Ho >= 1 && Wo >= 1, "maxpool3d: output would be empty");
   const long total = (long)N * Do * Ho * Wo * C;
   dim3 grid(ceil_div(total, 256)), block(256);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(maxpool3d_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, D,
-                       H, W, C, fz, fy, fx, Do, Ho, Wo, total);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(maxpool3d_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (float*)y, D, H,
-                       W, C, fz, fy, fx, Do, Ho, Wo, total);
-  else
-    PYTC_REQUIRE(false, "maxpool3d: bad dtype");
+  PYTC_DISPATCH_DTYPE(dtype, "maxpool3d", T,
+                      hipLaunchKernelGGL(maxpool3d_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)y, D, H, W, C, fz,
+                                         fy, fx, Do, Ho, Wo, total));
   PYTC_LAUNCH_CHECK("maxpool3d");
   return PYTC_OK;
 }
@@ -413,20 +392,13 @@ extern "C" int pytc_dwconvT3d_generic_fwd(const void* x, void* y, const float* w
   PYTC_REQUIRE(g.Do >= 1 && g.Ho >= 1 && g.Wo >= 1, "dwconvT3d_generic: empty output");
   const long total = (long)N * g.Do * g.Ho * g.Wo * C;
   dim3 grid(ceil_div(total, 256)), block(256);
-  if (dtype == PYTC_BF16 && C % 8 == 0)
-    hipLaunchKernelGGL((dwconvT3d_generic_vec_kernel<bf16_t, 8>), dim3(ceil_div(total / 8, 256)), block, 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (bf16_t*)y, w, g, total / 8);
-  else if (dtype == PYTC_F32 && C % 4 == 0)
-    hipLaunchKernelGGL((dwconvT3d_generic_vec_kernel<float, 4>), dim3(ceil_div(total / 4, 256)), block, 0, (hipStream_t)stream,
-                       (const float*)x, (float*)y, w, g, total / 4);
-  else if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(dwconvT3d_generic_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, w, g, total);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(dwconvT3d_generic_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (float*)y,
-                       w, g, total);
-  else
-    PYTC_REQUIRE(false, "dwconvT3d_generic: bad dtype");
+  PYTC_DISPATCH_DTYPE(dtype, "dwconvT3d_generic", T,
+    constexpr int V = elems_per_16b_of<T>;
+    if (C % V == 0)
+      hipLaunchKernelGGL((dwconvT3d_generic_vec_kernel<T, V>), dim3(ceil_div(total / V, 256)), block, 0, (hipStream_t)stream,
+                         (const T*)x, (T*)y, w, g, total / V);
+    else
+      hipLaunchKernelGGL(dwconvT3d_generic_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)y, w, g, total));
   PYTC_LAUNCH_CHECK("dwconvT3d_generic");
   return PYTC_OK;
 }
@@ -444,14 +416,9 @@ extern "C" int pytc_layernorm_rows(const void* x, void* y, const float* gamma, c
   const int rpb = 256 / (C / vec);
   long blocks = (rows + rpb - 1) / rpb;
   if (blocks > 65536) blocks = 65536;
-#define LN_LAUNCH(TT, V) hipLaunchKernelGGL((layernorm_rows_kernel<TT, V>), dim3((unsigned)blocks), dim3(256), 0, s, (const TT*)x, (TT*)y, gamma, beta, (long)rows, C, eps)
-  if (dtype == PYTC_BF16) {
-    if (vec == 8) LN_LAUNCH(bf16_t, 8); else if (vec == 4) LN_LAUNCH(bf16_t, 4); else if (vec == 2) LN_LAUNCH(bf16_t, 2); else LN_LAUNCH(bf16_t, 1);
-  } else if (dtype == PYTC_F32) {
-    if (vec == 8) LN_LAUNCH(float, 8); else if (vec == 4) LN_LAUNCH(float, 4); else if (vec == 2) LN_LAUNCH(float, 2); else LN_LAUNCH(float, 1);
-  } else {
-    PYTC_REQUIRE(false, "layernorm_rows: bad dtype");
-  }
+#define LN_LAUNCH(V) hipLaunchKernelGGL((layernorm_rows_kernel<T, V>), dim3((unsigned)blocks), dim3(256), 0, s, (const T*)x, (T*)y, gamma, beta, (long)rows, C, eps)
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_rows", T,
+                      if (vec == 8) LN_LAUNCH(8); else if (vec == 4) LN_LAUNCH(4); else if (vec == 2) LN_LAUNCH(2); else LN_LAUNCH(1));
 #undef LN_LAUNCH
   PYTC_LAUNCH_CHECK("layernorm_rows");
   return PYTC_OK;

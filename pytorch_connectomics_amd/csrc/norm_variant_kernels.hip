@@ -131,20 +131,15 @@ extern "C" int pytc_layernorm_rows_bwd(const void* dy, const void* x, const floa
   hipStream_t s = (hipStream_t)stream;
   const long blocks = ln_bwd_blocks((long)rows, C, vec);
   const size_t lds = (size_t)(256 / (C / vec)) * 2 * C * sizeof(float);       // = 256 * VEC * 8 bytes <= 16 KB
-#define LNB_LAUNCH(TT, V)                                                                                          \
-  hipLaunchKernelGGL((layernorm_rows_bwd_kernel<TT, V>), dim3((unsigned)blocks), dim3(256), lds, s, (const TT*)dy, \
-                     (const TT*)x, gamma, (TT*)dx, partial, (long)rows, C, eps)
-#define LNB_VEC(TT)                         \
-  switch (vec) {                            \
-    case 8: LNB_LAUNCH(TT, 8); break;       \
-    case 4: LNB_LAUNCH(TT, 4); break;       \
-    case 2: LNB_LAUNCH(TT, 2); break;       \
-    default: LNB_LAUNCH(TT, 1); break;      \
-  }
-  if (dtype == PYTC_BF16) { LNB_VEC(bf16_t) }
-  else if (dtype == PYTC_F32) { LNB_VEC(float) }
-  else { PYTC_REQUIRE(false, "layernorm_rows_bwd: bad dtype"); }
-#undef LNB_VEC
+#define LNB_LAUNCH(V)                                                                                            \
+  hipLaunchKernelGGL((layernorm_rows_bwd_kernel<T, V>), dim3((unsigned)blocks), dim3(256), lds, s, (const T*)dy, \
+                     (const T*)x, gamma, (T*)dx, partial, (long)rows, C, eps)
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_rows_bwd", T, switch (vec) {
+    case 8: LNB_LAUNCH(8); break;
+    case 4: LNB_LAUNCH(4); break;
+    case 2: LNB_LAUNCH(2); break;
+    default: LNB_LAUNCH(1); break;
+  });
 #undef LNB_LAUNCH
   PYTC_LAUNCH_CHECK("layernorm_rows_bwd");
   return PYTC_OK;
@@ -157,14 +152,9 @@ extern "C" int pytc_grn_bwd_apply(const void* dh2, const void* hp, const float* 
   const long total = (long)N * rows * C;
   long blocks = (total + 255) / 256;
   if (blocks > 65536) blocks = 65536;
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(grn_bwd_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)dh2,
-                       (const bf16_t*)hp, A, B, (bf16_t*)out, (long)rows, C, total);
-  else if (dtype == PYTC_F32)
-    hipLaunchKernelGGL(grn_bwd_apply_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)dh2,
-                       (const float*)hp, A, B, (float*)out, (long)rows, C, total);
-  else
-    PYTC_REQUIRE(false, "grn_bwd_apply: bad dtype");
+  PYTC_DISPATCH_DTYPE(dtype, "grn_bwd_apply", T,
+                      hipLaunchKernelGGL(grn_bwd_apply_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)dh2,
+                                         (const T*)hp, A, B, (T*)out, (long)rows, C, total));
   PYTC_LAUNCH_CHECK("grn_bwd_apply");
   return PYTC_OK;
 }

@@ -42,6 +42,10 @@ struct Mma<float> {
   }
 };
 
+static_assert(Mma<bf16_t>::KSTEP == mfma_kstep(PYTC_BF16) && Mma<float>::KSTEP == mfma_kstep(PYTC_F32) &&
+                  Mma<bf16_t>::EPL == elems_per_16b(PYTC_BF16) && Mma<float>::EPL == elems_per_16b(PYTC_F32),
+              "the host helpers of pytc_common.h must agree with the fragment traits");
+
 // Row permutation used by the "paired" packing: two consecutive 16-row tiles (T = 2p, 2p+1) are
 // interleaved so that the MFMA C/D layout (lane group kb owns rows 4kb..4kb+3 of each tile) leaves
 // every lane with 8 CONSECUTIVE logical rows p*32 + kb*8 + 0..7:

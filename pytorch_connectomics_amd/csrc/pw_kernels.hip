@@ -224,27 +224,22 @@ using namespace pytc;
 extern "C" int pytc_pw_conv_paired_supported(const pytc_pw_args* a) { return a && pw_fast_supported(a) ? 1 : 0; }
 extern "C" int pytc_pw_conv_rowmajor_supported(const pytc_pw_args* a) { return a && pw_gemm_rowmajor_supported(a) ? 1 : 0; }
 
-static int kstep_of(int dtype) { return dtype == PYTC_BF16 ? 32 : 16; }
-
 extern "C" int64_t pytc_pw_packed_elems(int C_out, int C_in, int dtype) {
   if (C_out < 1 || C_in < 1 || (dtype != PYTC_F32 && dtype != PYTC_BF16)) return -1;
-  int ks = kstep_of(dtype);
+  int ks = mfma_kstep(dtype);
   return (int64_t)((C_out + 15) / 16) * 16 * ((C_in + ks - 1) / ks) * ks;
 }
 
 extern "C" int pytc_pw_pack_weight(const float* w, int C_out, int C_in, int transposed, void* packed, int dtype,
                                    void* stream) {
   PYTC_REQUIRE(w && packed && C_out >= 1 && C_in >= 1, "pw_pack_weight: bad arguments");
-  PYTC_REQUIRE(dtype == PYTC_F32 || dtype == PYTC_BF16, "pw_pack_weight: bad dtype");
+  PYTC_CHECK_DTYPE(dtype, "pw_pack_weight");
   long total = pytc_pw_packed_elems(C_out, C_in, dtype);
-  int KG = (C_in + kstep_of(dtype) - 1) / kstep_of(dtype);
+  int KG = (C_in + mfma_kstep(dtype) - 1) / mfma_kstep(dtype);
   dim3 grid(ceil_div(total, 256)), block(256);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(pw_pack_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, transposed,
-                       (bf16_t*)packed, KG, total);
-  else
-    hipLaunchKernelGGL(pw_pack_kernel<float>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, transposed,
-                       (float*)packed, KG, total);
+  PYTC_DISPATCH_DTYPE(dtype, "pw_pack_weight", T,
+                      hipLaunchKernelGGL(pw_pack_kernel<T>, grid, block, 0, (hipStream_t)stream, w, C_out, C_in, transposed, (T*)packed, KG,
+                                         total));
   PYTC_LAUNCH_CHECK("pw_pack_weight");
   return PYTC_OK;
 }
@@ -252,7 +247,7 @@ extern "C" int pytc_pw_pack_weight(const float* w, int C_out, int C_in, int tran
 extern "C" int pytc_pw_conv_fwd(const pytc_pw_args* a, void* stream) {
   PYTC_REQUIRE(a && a->x && a->w_packed && a->y, "pw_conv: null pointer");
   PYTC_REQUIRE(a->N >= 1 && a->rows_per_sample >= 1 && a->C_in >= 1 && a->C_out >= 1, "pw_conv: bad shape");
-  PYTC_REQUIRE(a->w_dtype == PYTC_F32 || a->w_dtype == PYTC_BF16, "pw_conv: bad w_dtype");
+  PYTC_CHECK_DTYPE(a->w_dtype, "pw_conv");
   PYTC_REQUIRE(a->res_mode == PYTC_RES_NONE || a->res, "pw_conv: residual mode without residual pointer");
   PYTC_REQUIRE(a->res_mode != PYTC_RES_NORM_BWD || (a->w_paired && a->res_bias),
                "pw_conv: RES_NORM_BWD runs on the paired-row kernel and needs its coefficients in res_bias");
@@ -262,7 +257,7 @@ extern "C" int pytc_pw_conv_fwd(const pytc_pw_args* a, void* stream) {
   p.e.rps_out = a->rows_per_sample; p.e.C_out = a->C_out; p.e.res_mode = a->res_mode; p.e.nt = 0;
   p.e.Go_d = p.e.Go_h = p.e.Go_w = p.e.Gl_d = p.e.Gl_h = p.e.Gl_w = 0;
   p.N = a->N; p.C_in = a->C_in; p.C_out = a->C_out;
-  p.KG = (a->C_in + kstep_of(a->w_dtype) - 1) / kstep_of(a->w_dtype);
+  p.KG = (a->C_in + mfma_kstep(a->w_dtype) - 1) / mfma_kstep(a->w_dtype);
   p.MTt = (a->C_out + 15) / 16;
   p.act = a->act; p.gather = a->gather; p.pre_act = a->pre_act;
   PYTC_REQUIRE(a->pre_act == PYTC_ACT_NONE || a->pre_act == PYTC_ACT_GELU, "pw_conv: bad pre_act");
@@ -299,15 +294,13 @@ extern "C" int pytc_pw_conv_fwd(const pytc_pw_args* a, void* stream) {
   if (plain && a->C_in == 1 && a->C_out % 8 == 0 && 256 % (a->C_out / 8) == 0 && tw == PYTC_BF16 && (ti == PYTC_F32 || ti == PYTC_BF16) && to == PYTC_BF16) {
     const long work = rows_total * (a->C_out / 8);
     const int blocks = (int)(ceil_div(work, 256) < 8192 ? ceil_div(work, 256) : 8192);
-    if (ti == PYTC_F32) hipLaunchKernelGGL((pw_stem_kernel<float, bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, s, (const float*)a->x, (const bf16_t*)a->w_packed, a->bias, (bf16_t*)a->y, rows_total, a->C_out, a->act);
-    else hipLaunchKernelGGL((pw_stem_kernel<bf16_t, bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)a->x, (const bf16_t*)a->w_packed, a->bias, (bf16_t*)a->y, rows_total, a->C_out, a->act);
+    PYTC_DISPATCH_DTYPE(ti, "pw_conv", TI, hipLaunchKernelGGL((pw_stem_kernel<TI, bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, s, (const TI*)a->x, (const bf16_t*)a->w_packed, a->bias, (bf16_t*)a->y, rows_total, a->C_out, a->act));
     PYTC_LAUNCH_CHECK("pw_conv");
     return PYTC_OK;
   }
   if (plain && a->C_out == 1 && ti == PYTC_BF16 && tw == PYTC_BF16 && a->C_in >= 8 && a->C_in <= 512 && (a->C_in & (a->C_in - 1)) == 0) {
     const long work = rows_total * (a->C_in / 8);
-    if (to == PYTC_F32) hipLaunchKernelGGL((pw_head_kernel<bf16_t, float>), dim3(ceil_div(work, 256)), dim3(256), 0, s, (const bf16_t*)a->x, (const bf16_t*)a->w_packed, a->bias, (float*)a->y, rows_total, a->C_in, a->act);
-    else hipLaunchKernelGGL((pw_head_kernel<bf16_t, bf16_t>), dim3(ceil_div(work, 256)), dim3(256), 0, s, (const bf16_t*)a->x, (const bf16_t*)a->w_packed, a->bias, (bf16_t*)a->y, rows_total, a->C_in, a->act);
+    PYTC_DISPATCH_DTYPE(to, "pw_conv", TO, hipLaunchKernelGGL((pw_head_kernel<bf16_t, TO>), dim3(ceil_div(work, 256)), dim3(256), 0, s, (const bf16_t*)a->x, (const bf16_t*)a->w_packed, a->bias, (TO*)a->y, rows_total, a->C_in, a->act));
     PYTC_LAUNCH_CHECK("pw_conv");
     return PYTC_OK;
   }

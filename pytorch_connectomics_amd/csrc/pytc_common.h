@@ -43,6 +43,35 @@ bool take_launch_failure();   // a launch helper gave up before launching (error
     if (e_ != hipSuccess) return pytc::hip_fail(e_, name);       \
   } while (0)
 
+// ---- storage dtype: the ONE place a dtype code becomes an element type.  PYTC_DISPATCH_DTYPE runs its body (the rest of the macro's
+// arguments, commas and all) with `T` bound to bf16_t or float; any other code sets "<what>: bad dtype <code>" and returns
+// PYTC_ERR_INVALID from the enclosing entry point, so no launch is reachable with a code that is not one of the two.  PYTC_REQUIRE /
+// PYTC_LAUNCH_CHECK keep working inside the body.  PYTC_CHECK_DTYPE is the same refusal alone, for an entry that launches something
+// untyped first or plans by dtype before it launches.
+#define PYTC_CHECK_DTYPE(dtype, what) \
+  PYTC_REQUIRE((dtype) == PYTC_BF16 || (dtype) == PYTC_F32, "%s: bad dtype %d", what, (int)(dtype))
+
+#define PYTC_DISPATCH_DTYPE(dtype, what, T, ...)      \
+  do {                                                \
+    if ((dtype) == PYTC_BF16) {                       \
+      using T = pytc::bf16_t;                         \
+      __VA_ARGS__;                                    \
+    } else if ((dtype) == PYTC_F32) {                 \
+      using T = float;                                \
+      __VA_ARGS__;                                    \
+    } else {                                          \
+      PYTC_CHECK_DTYPE(dtype, what);                  \
+    }                                                 \
+  } while (0)
+
+// the two numbers a launch derives from the storage dtype: elements of one 16-byte vector, and the k covered by one MFMA fragment set
+// (Mma<T>::KSTEP of pw_common.h, which asserts the agreement)
+constexpr int elems_per_16b(int dtype) { return dtype == PYTC_BF16 ? 8 : 4; }
+constexpr int mfma_kstep(int dtype) { return dtype == PYTC_BF16 ? 32 : 16; }
+template <typename T>
+constexpr int elems_per_16b_of = 16 / (int)sizeof(T);       // the same width as a template argument, inside a dispatch body
+static_assert(elems_per_16b_of<__bf16> == elems_per_16b(PYTC_BF16) && elems_per_16b_of<float> == elems_per_16b(PYTC_F32), "one width rule");
+
 // ---- tuning knobs: the CLOSED set of keys pytc_set_tuning / PYTC_TUNING accept, one row each: name, default, meaning.  Every knob
 // selects the kernel form an A/B parity test compares against the default (tests/); a row is the only place a default is written.
 #define PYTC_KNOBS(X)                                                                                                             \

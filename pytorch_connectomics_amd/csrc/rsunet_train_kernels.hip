@@ -777,10 +777,6 @@ bn_train_finalize_kernel(const float* __restrict__ stats, int slots, float count
 
 using namespace pytc;
 
-#define RS_DISPATCH(dtype, BF, F32, what)                                   \
-  if (dtype == PYTC_BF16) { BF; } else if (dtype == PYTC_F32) { F32; } else { \
-    set_error(what ": bad dtype %d", dtype); return PYTC_ERR_INVALID; }
-
 // launch plan shared by the workspace query and the launch
 struct CwPlan { bool mfma, rag_o, rag_k; int mt, nt, kp, tiles, slots; long per_slot; };
 // one input and one output channel, 3^3 taps (the last conv of a single-class U-Net): a 27-bin correlation of two scalar fields
@@ -886,10 +882,8 @@ extern "C" int pytc_conv3d_wgrad(const void* a, const void* dy, float* dW, float
   const int taps = g.kd * g.kh * g.kw;
   hipStream_t s = (hipStream_t)stream;
   if (cw_scalar(C_in, C_out, kernel, dtype)) {
-    RS_DISPATCH(dtype,
-                hipLaunchKernelGGL(conv3d_wgrad_scalar_kernel<bf16_t>, dim3(slots), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)dy, workspace, N, D, H, W, p.per_slot, rows_total),
-                hipLaunchKernelGGL(conv3d_wgrad_scalar_kernel<float>, dim3(slots), dim3(256), 0, s, (const float*)a, (const float*)dy, workspace, N, D, H, W, p.per_slot, rows_total),
-                "conv3d_wgrad")
+    PYTC_DISPATCH_DTYPE(dtype, "conv3d_wgrad", T,
+                        hipLaunchKernelGGL(conv3d_wgrad_scalar_kernel<T>, dim3(slots), dim3(256), 0, s, (const T*)a, (const T*)dy, workspace, N, D, H, W, p.per_slot, rows_total));
   } else if (p.mfma) {
     const long blocks = (long)((slots + 7) / 8) * 8 * p.tiles * g.kd;
     const bf16_t* ap = (const bf16_t*)a;
@@ -911,10 +905,8 @@ extern "C" int pytc_conv3d_wgrad(const void* a, const void* dy, float* dW, float
   } else {
     const long rps = p.per_slot;
     dim3 grid(slots, ((C_out + CW_TO - 1) / CW_TO) * ((C_in + CW_TK - 1) / CW_TK), taps), block(256);
-    RS_DISPATCH(dtype,
-                hipLaunchKernelGGL(conv3d_wgrad_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)a, (const bf16_t*)dy, workspace, rows_total, g, C_in, C_out, rps, slots),
-                hipLaunchKernelGGL(conv3d_wgrad_kernel<float>, grid, block, 0, s, (const float*)a, (const float*)dy, workspace, rows_total, g, C_in, C_out, rps, slots),
-                "conv3d_wgrad")
+    PYTC_DISPATCH_DTYPE(dtype, "conv3d_wgrad", T,
+                        hipLaunchKernelGGL(conv3d_wgrad_kernel<T>, grid, block, 0, s, (const T*)a, (const T*)dy, workspace, rows_total, g, C_in, C_out, rps, slots));
   }
   const long nW = (long)taps * C_out * C_in;
   hipLaunchKernelGGL(reduce_slots2_kernel, dim3(ceil_div(nW, 16)), dim3(256), 0, s, workspace, dW, nW, slots);
@@ -927,22 +919,16 @@ extern "C" int pytc_act_bwd(const void* da, const void* x, const float* ab, void
   PYTC_REQUIRE(da && x && dt && N >= 1 && rows >= 1 && C >= 1, "act_bwd: bad arguments");
   const long total = (long)N * rows * C;
   hipStream_t s = (hipStream_t)stream;
-  {
-    const int vec = dtype == PYTC_BF16 ? 8 : 4;
-    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
-      const long chunks = total / vec;
-      if (dtype == PYTC_BF16)
-        hipLaunchKernelGGL(act_bwd_vec_kernel<bf16_t>, dim3(grid_for(chunks)), dim3(256), 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, (bf16_t*)dt, (bf16_t*)dp, (long)rows, C, chunks, act, prm);
-      else
-        hipLaunchKernelGGL(act_bwd_vec_kernel<float>, dim3(grid_for(chunks)), dim3(256), 0, s, (const float*)da, (const float*)x, ab, (float*)dt, (float*)dp, (long)rows, C, chunks, act, prm);
-      PYTC_LAUNCH_CHECK("act_bwd");
-      return PYTC_OK;
-    }
+  const int vec = elems_per_16b(dtype);
+  if (C % vec == 0 && tuning_get(K_elementwise_vec)) {
+    const long chunks = total / vec;
+    PYTC_DISPATCH_DTYPE(dtype, "act_bwd", T,
+                        hipLaunchKernelGGL(act_bwd_vec_kernel<T>, dim3(grid_for(chunks)), dim3(256), 0, s, (const T*)da, (const T*)x, ab, (T*)dt, (T*)dp, (long)rows, C, chunks, act, prm));
+    PYTC_LAUNCH_CHECK("act_bwd");
+    return PYTC_OK;
   }
-  RS_DISPATCH(dtype,
-              hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, (bf16_t*)dt, (bf16_t*)dp, (long)rows, C, total, act, prm),
-              hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)da, (const float*)x, ab, (float*)dt, (float*)dp, (long)rows, C, total, act, prm),
-              "act_bwd")
+  PYTC_DISPATCH_DTYPE(dtype, "act_bwd", T,
+                      hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const T*)da, (const T*)x, ab, (T*)dt, (T*)dp, (long)rows, C, total, act, prm));
   PYTC_LAUNCH_CHECK("act_bwd");
   return PYTC_OK;
 }
@@ -952,22 +938,16 @@ extern "C" int pytc_norm_bwd_apply_general(const void* d, const void* x, const f
   PYTC_REQUIRE(d && x && mean_rstd && M && dx, "norm_bwd_apply_general: null pointer");
   const long total = (long)N * rows * C;
   hipStream_t s = (hipStream_t)stream;
-  {
-    const int vec = dtype == PYTC_BF16 ? 8 : 4;
-    if ((dtype == PYTC_BF16 || dtype == PYTC_F32) && C % vec == 0 && tuning_get(K_elementwise_vec)) {
-      const long chunks = total / vec;
-      if (dtype == PYTC_BF16)
-        hipLaunchKernelGGL(norm_bwd_apply_general_vec_kernel<bf16_t>, dim3(grid_for(chunks)), dim3(256), 0, s, (const bf16_t*)d, (const bf16_t*)x, mean_rstd, gamma, M, (bf16_t*)dx, (long)rows, C, chunks);
-      else
-        hipLaunchKernelGGL(norm_bwd_apply_general_vec_kernel<float>, dim3(grid_for(chunks)), dim3(256), 0, s, (const float*)d, (const float*)x, mean_rstd, gamma, M, (float*)dx, (long)rows, C, chunks);
-      PYTC_LAUNCH_CHECK("norm_bwd_apply_general");
-      return PYTC_OK;
-    }
+  const int vec = elems_per_16b(dtype);
+  if (C % vec == 0 && tuning_get(K_elementwise_vec)) {
+    const long chunks = total / vec;
+    PYTC_DISPATCH_DTYPE(dtype, "norm_bwd_apply_general", T,
+                        hipLaunchKernelGGL(norm_bwd_apply_general_vec_kernel<T>, dim3(grid_for(chunks)), dim3(256), 0, s, (const T*)d, (const T*)x, mean_rstd, gamma, M, (T*)dx, (long)rows, C, chunks));
+    PYTC_LAUNCH_CHECK("norm_bwd_apply_general");
+    return PYTC_OK;
   }
-  RS_DISPATCH(dtype,
-              hipLaunchKernelGGL(norm_bwd_apply_general_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)d, (const bf16_t*)x, mean_rstd, gamma, M, (bf16_t*)dx, (long)rows, C, total),
-              hipLaunchKernelGGL(norm_bwd_apply_general_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)d, (const float*)x, mean_rstd, gamma, M, (float*)dx, (long)rows, C, total),
-              "norm_bwd_apply_general")
+  PYTC_DISPATCH_DTYPE(dtype, "norm_bwd_apply_general", T,
+                      hipLaunchKernelGGL(norm_bwd_apply_general_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const T*)d, (const T*)x, mean_rstd, gamma, M, (T*)dx, (long)rows, C, total));
   PYTC_LAUNCH_CHECK("norm_bwd_apply_general");
   return PYTC_OK;
 }
@@ -980,18 +960,15 @@ extern "C" int pytc_act_norm_bwd_stats(const void* da, const void* x, const floa
                                        int dtype, void* stream) {
   PYTC_REQUIRE(da && x && mean_rstd && stats_ws && s_out && N >= 1 && rows >= 1, "act_norm_bwd_stats: bad arguments");
   PYTC_REQUIRE((p_ws == nullptr) == (p_out == nullptr), "act_norm_bwd_stats: p_ws and p_out come as a pair");
-  PYTC_REQUIRE((dtype == PYTC_BF16 && C % 8 == 0) || (dtype == PYTC_F32 && C % 4 == 0), "act_norm_bwd_stats: C %% (16 bytes) != 0");
-  const int slots = act_norm_slots(rows, C, dtype == PYTC_BF16 ? 8 : 4);      // <= colstats_slots(rows): the workspace bound
+  PYTC_CHECK_DTYPE(dtype, "act_norm_bwd_stats");
+  PYTC_REQUIRE(C % elems_per_16b(dtype) == 0, "act_norm_bwd_stats: C %% (16 bytes) != 0");
+  const int slots = act_norm_slots(rows, C, elems_per_16b(dtype));      // <= colstats_slots(rows): the workspace bound
   const long rps = (rows + slots - 1) / slots;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(slots, N), block(256);
-  if (dtype == PYTC_BF16) {
-    if (p_ws) hipLaunchKernelGGL((act_norm_bwd_stats_kernel<bf16_t, true>), grid, block, 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm);
-    else hipLaunchKernelGGL((act_norm_bwd_stats_kernel<bf16_t, false>), grid, block, 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm);
-  } else {
-    if (p_ws) hipLaunchKernelGGL((act_norm_bwd_stats_kernel<float, true>), grid, block, 0, s, (const float*)da, (const float*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm);
-    else hipLaunchKernelGGL((act_norm_bwd_stats_kernel<float, false>), grid, block, 0, s, (const float*)da, (const float*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "act_norm_bwd_stats", T,
+    if (p_ws) hipLaunchKernelGGL((act_norm_bwd_stats_kernel<T, true>), grid, block, 0, s, (const T*)da, (const T*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm);
+    else hipLaunchKernelGGL((act_norm_bwd_stats_kernel<T, false>), grid, block, 0, s, (const T*)da, (const T*)x, ab, mean_rstd, stats_ws, p_ws, (long)rows, C, slots, rps, act, prm));
   hipLaunchKernelGGL(reduce_slots_batched_rs_kernel, dim3(ceil_div(2L * C, 16), N), dim3(256), 0, s, stats_ws, s_out, 2L * C, slots);
   if (p_ws) hipLaunchKernelGGL(reduce_slots_batched_rs_kernel, dim3(ceil_div((long)C, 16), N), dim3(256), 0, s, p_ws, p_out, (long)C, slots);
   PYTC_LAUNCH_CHECK("act_norm_bwd_stats");
@@ -1019,15 +996,14 @@ extern "C" int pytc_act_norm_bwd_apply_cg(const void* da, const void* x, const f
 static int act_norm_bwd_apply_impl(const void* da, const void* x, const float* ab, const float* mean_rstd, const float* gamma, int C_gamma,
                                    const float* M, void* dx, int N, int64_t rows, int C, int act, float prm, int dtype, void* stream) {
   PYTC_REQUIRE(da && x && mean_rstd && M && dx, "act_norm_bwd_apply: null pointer");
-  PYTC_REQUIRE((dtype == PYTC_BF16 && C % 8 == 0) || (dtype == PYTC_F32 && C % 4 == 0), "act_norm_bwd_apply: C %% (16 bytes) != 0");
-  const int slots = act_norm_slots(rows, C, dtype == PYTC_BF16 ? 8 : 4);
+  PYTC_CHECK_DTYPE(dtype, "act_norm_bwd_apply");
+  PYTC_REQUIRE(C % elems_per_16b(dtype) == 0, "act_norm_bwd_apply: C %% (16 bytes) != 0");
+  const int slots = act_norm_slots(rows, C, elems_per_16b(dtype));
   const long rps = (rows + slots - 1) / slots;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(slots, N), block(256);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(act_norm_bwd_apply_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)da, (const bf16_t*)x, ab, mean_rstd, gamma, M, (bf16_t*)dx, (long)rows, C, rps, act, prm, C_gamma);
-  else
-    hipLaunchKernelGGL(act_norm_bwd_apply_kernel<float>, grid, block, 0, s, (const float*)da, (const float*)x, ab, mean_rstd, gamma, M, (float*)dx, (long)rows, C, rps, act, prm, C_gamma);
+  PYTC_DISPATCH_DTYPE(dtype, "act_norm_bwd_apply", T,
+                      hipLaunchKernelGGL(act_norm_bwd_apply_kernel<T>, grid, block, 0, s, (const T*)da, (const T*)x, ab, mean_rstd, gamma, M, (T*)dx, (long)rows, C, rps, act, prm, C_gamma));
   PYTC_LAUNCH_CHECK("act_norm_bwd_apply");
   return PYTC_OK;
 }
@@ -1038,12 +1014,11 @@ extern "C" int pytc_maxpool3d_bwd(const void* x, const void* dy, void* dx, int N
   const int Do = D / fz, Ho = H / fy, Wo = W / fx;
   const long total = (long)N * Do * Ho * Wo * C;
   hipStream_t s = (hipStream_t)stream;
-  const size_t bytes = (size_t)N * D * H * W * C * (dtype == PYTC_BF16 ? 2 : 4);
+  PYTC_CHECK_DTYPE(dtype, "maxpool3d_bwd");
+  const size_t bytes = (size_t)N * D * H * W * C * (16 / elems_per_16b(dtype));
   if (hipMemsetAsync(dx, 0, bytes, s) != hipSuccess) { set_error("maxpool3d_bwd: memset failed"); return PYTC_ERR_HIP; }
-  RS_DISPATCH(dtype,
-              hipLaunchKernelGGL(maxpool3d_bwd_kernel<bf16_t>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, D, H, W, C, fz, fy, fx, Do, Ho, Wo, total),
-              hipLaunchKernelGGL(maxpool3d_bwd_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)dx, D, H, W, C, fz, fy, fx, Do, Ho, Wo, total),
-              "maxpool3d_bwd")
+  PYTC_DISPATCH_DTYPE(dtype, "maxpool3d_bwd", T,
+                      hipLaunchKernelGGL(maxpool3d_bwd_kernel<T>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const T*)x, (const T*)dy, (T*)dx, D, H, W, C, fz, fy, fx, Do, Ho, Wo, total));
   PYTC_LAUNCH_CHECK("maxpool3d_bwd");
   return PYTC_OK;
 }
@@ -1056,10 +1031,8 @@ extern "C" int pytc_dwconv3d_generic_fwd(const void* x, void* y, const float* w,
           out_dims[0], out_dims[1], out_dims[2]};
   const long total = (long)N * g.Do * g.Ho * g.Wo * C;
   hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH(dtype,
-              hipLaunchKernelGGL(dwconv3d_generic_kernel<bf16_t>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, w, g, total),
-              hipLaunchKernelGGL(dwconv3d_generic_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const float*)x, (float*)y, w, g, total),
-              "dwconv3d_generic")
+  PYTC_DISPATCH_DTYPE(dtype, "dwconv3d_generic", T,
+                      hipLaunchKernelGGL(dwconv3d_generic_kernel<T>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const T*)x, (T*)y, w, g, total));
   PYTC_LAUNCH_CHECK("dwconv3d_generic");
   return PYTC_OK;
 }

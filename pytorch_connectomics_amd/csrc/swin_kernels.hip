@@ -227,16 +227,12 @@ extern "C" int pytc_window_partition(const void* src, void* dst, const void* res
   WinGeo g;
   if (int s = win_geo("window_partition", geom, &g)) return s;
   PYTC_REQUIRE(src && dst && B >= 1 && C >= 1 && (!res || reverse), "window_partition: bad arguments");
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "window_partition: bad dtype");
   const long rows = reverse ? (long)B * g.G[0] * g.G[1] * g.G[2] : (long)B * g.P[0] * g.P[1] * g.P[2];
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(window_gather_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, (const bf16_t*)res, g, rows,
-                       C, reverse);
-  else
-    hipLaunchKernelGGL(window_gather_kernel<float>, grid, dim3(256), 0, st, (const float*)src, (float*)dst, (const float*)res, g, rows, C,
-                       reverse);
+  PYTC_DISPATCH_DTYPE(dtype, "window_partition", T,
+                      hipLaunchKernelGGL(window_gather_kernel<T>, grid, dim3(256), 0, st, (const T*)src, (T*)dst, (const T*)res, g, rows, C,
+                                         reverse));
   PYTC_LAUNCH_CHECK("window_partition");
   return PYTC_OK;
 }
@@ -246,20 +242,18 @@ extern "C" int pytc_space_to_depth2(const void* src, void* dst, int B, int D, in
   PYTC_REQUIRE(src && dst && B >= 1 && C >= 1 && D >= 2 && H >= 2 && W >= 2 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0,
                "space_to_depth2: grid (%d, %d, %d) is not a whole number of 2^3 cells", D, H, W);
   PYTC_REQUIRE(order == 0 || order == 1, "space_to_depth2: order %d (0: conv taps, 1: PatchMerging v1)", order);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "space_to_depth2: bad dtype");
   const long rows = scatter ? (long)B * D * H * W : (long)B * (D / 2) * (H / 2) * (W / 2);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(s2d_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, D, H, W, C, rows, order, scatter);
-  else hipLaunchKernelGGL(s2d_kernel<float>, grid, dim3(256), 0, st, (const float*)src, (float*)dst, D, H, W, C, rows, order, scatter);
+  PYTC_DISPATCH_DTYPE(dtype, "space_to_depth2", T,
+                      hipLaunchKernelGGL(s2d_kernel<T>, grid, dim3(256), 0, st, (const T*)src, (T*)dst, D, H, W, C, rows, order, scatter));
   PYTC_LAUNCH_CHECK("space_to_depth2");
   return PYTC_OK;
 }
 
 static int ln_any_check(const char* what, int64_t rows, int C, int dtype) {
   PYTC_REQUIRE(rows >= 1 && C >= 16 && C <= 6144 && C % 16 == 0, "%s: C = %d must be a multiple of 16 in [16, 6144]", what, C);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   return PYTC_OK;
 }
 
@@ -269,9 +263,8 @@ extern "C" int pytc_layernorm_any(const void* x, void* y, const float* gamma, co
   PYTC_REQUIRE(x && y && !gamma == !beta, "layernorm_any: null pointer (gamma and beta are both given or both null)");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(layernorm_any_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, gamma, beta, (long)rows, C, eps);
-  else hipLaunchKernelGGL(layernorm_any_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)y, gamma, beta, (long)rows, C, eps);
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_any", T,
+                      hipLaunchKernelGGL(layernorm_any_fwd_kernel<T>, grid, dim3(256), 0, st, (const T*)x, (T*)y, gamma, beta, (long)rows, C, eps));
   PYTC_LAUNCH_CHECK("layernorm_any");
   return PYTC_OK;
 }
@@ -286,24 +279,16 @@ extern "C" int pytc_layernorm_any_bwd(const void* dy, const void* x, const float
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
   float2* s2 = dgamma ? reinterpret_cast<float2*>(stats) : nullptr;
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(layernorm_any_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, gamma, (bf16_t*)dx, s2,
-                       (long)rows, C, eps);
-  else
-    hipLaunchKernelGGL(layernorm_any_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)dy, (const float*)x, gamma, (float*)dx, s2,
-                       (long)rows, C, eps);
-  if (dgamma) {
-    const int slots = ceil_div(rows, LNA_ROWS_PER_SLOT);
-    dim3 pg(ceil_div(C, 256), slots);
-    if (dtype == PYTC_BF16)
-      hipLaunchKernelGGL(layernorm_any_param_kernel<bf16_t>, pg, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const float2*)s2,
-                         partial, (long)rows, C);
-    else
-      hipLaunchKernelGGL(layernorm_any_param_kernel<float>, pg, dim3(256), 0, st, (const float*)dy, (const float*)x, (const float2*)s2,
-                         partial, (long)rows, C);
+  const int slots = ceil_div(rows, LNA_ROWS_PER_SLOT);
+  dim3 pg(ceil_div(C, 256), slots);
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_any_bwd", T,
+    hipLaunchKernelGGL(layernorm_any_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)dy, (const T*)x, gamma, (T*)dx, s2, (long)rows, C, eps);
+    if (dgamma)
+      hipLaunchKernelGGL(layernorm_any_param_kernel<T>, pg, dim3(256), 0, st, (const T*)dy, (const T*)x, (const float2*)s2, partial,
+                         (long)rows, C));
+  if (dgamma)
     hipLaunchKernelGGL(layernorm_any_reduce_kernel, dim3(ceil_div(2 * C, 256)), dim3(256), 0, st, (const float*)partial, dgamma, dbeta,
                        slots, C);
-  }
   PYTC_LAUNCH_CHECK("layernorm_any_bwd");
   return PYTC_OK;
 }

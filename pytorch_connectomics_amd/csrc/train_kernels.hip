@@ -1635,18 +1635,11 @@ static int grid_for(long n) { long b = (n + 255) / 256; return (int)(b < 16384 ?
 
 using namespace pytc;
 
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32, name)                 \
-  if ((dtype) == PYTC_BF16) { CALL_BF16; }                            \
-  else if ((dtype) == PYTC_F32) { CALL_F32; }                         \
-  else { PYTC_REQUIRE(false, name ": bad dtype"); }
-
 extern "C" int pytc_gelu(const void* x, const void* dy, void* out, int64_t n, int dtype, void* stream) {
   PYTC_REQUIRE(x && out && n > 0, "gelu: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(gelu_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, (long)n),
-             hipLaunchKernelGGL(gelu_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, (const float*)x, (const float*)dy, (float*)out, (long)n),
-             "gelu")
+  PYTC_DISPATCH_DTYPE(dtype, "gelu", T,
+                      hipLaunchKernelGGL(gelu_kernel<T>, dim3(grid_for(n)), dim3(256), 0, s, (const T*)x, (const T*)dy, (T*)out, (long)n));
   PYTC_LAUNCH_CHECK("gelu");
   return PYTC_OK;
 }
@@ -1654,17 +1647,16 @@ extern "C" int pytc_gelu(const void* x, const void* dy, void* out, int64_t n, in
 extern "C" int pytc_add_inplace(void* y, const void* x, int64_t n, int dtype, void* stream) {
   PYTC_REQUIRE(x && y && n > 0, "add_inplace: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, s, (bf16_t*)y, (const bf16_t*)x, (long)n),
-             hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(n)), dim3(256), 0, s, (float*)y, (const float*)x, (long)n),
-             "add_inplace")
+  PYTC_DISPATCH_DTYPE(dtype, "add_inplace", T,
+                      hipLaunchKernelGGL(add_kernel<T>, dim3(grid_for(n)), dim3(256), 0, s, (T*)y, (const T*)x, (long)n));
   PYTC_LAUNCH_CHECK("add_inplace");
   return PYTC_OK;
 }
 
 extern "C" int pytc_copy_zero_front(const void* src, void* dst, int N, const int32_t* dims, int C, int dtype, void* stream) {
   PYTC_REQUIRE(src && dst && dims && N >= 1 && dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && C >= 1, "copy_zero_front: bad arguments");
-  const int esz = dtype == PYTC_BF16 ? 2 : 4;
+  PYTC_CHECK_DTYPE(dtype, "copy_zero_front");
+  const int esz = 16 / elems_per_16b(dtype);
   PYTC_REQUIRE((C * esz) % 16 == 0, "copy_zero_front: a voxel's channels must be a multiple of 16 bytes (C = %d)", C);
   const int ppv = C * esz / 16;
   const long pieces = (long)N * dims[0] * dims[1] * dims[2] * ppv;
@@ -1744,21 +1736,17 @@ static int pw_wgrad_impl(const void* x, const float* ab, const void* dy, float* 
     if (mt == 4) launch_wgrad_mfma<4>(nt, grid, s, xp, ab, dp, dWp, dbq, rows_total, (long)rows_per_sample, C_in, C_out, rps, x_act);
     else if (mt == 2) launch_wgrad_mfma<2>(nt, grid, s, xp, ab, dp, dWp, dbq, rows_total, (long)rows_per_sample, C_in, C_out, rps, x_act);
     else launch_wgrad_mfma<1>(nt, grid, s, xp, ab, dp, dWp, dbq, rows_total, (long)rows_per_sample, C_in, C_out, rps, x_act);
-  } else if (!ab && x_act == PYTC_ACT_NONE && (C_in == 1 || C_out == 1) && (C_in * C_out) % (dtype == PYTC_BF16 ? 8 : 4) == 0 &&
-             C_in * C_out <= (dtype == PYTC_BF16 ? 2048 : 1024)) {
+  } else if (!ab && x_act == PYTC_ACT_NONE && (C_in == 1 || C_out == 1) && (C_in * C_out) % elems_per_16b(dtype) == 0 &&
+             C_in * C_out <= 256 * elems_per_16b(dtype)) {
     const int Cb = C_in * C_out, big_is_dy = C_in == 1;
     const void* big = big_is_dy ? dy : x;
     const void* thin = big_is_dy ? x : dy;
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(pw_wgrad_thin_kernel<bf16_t>, dim3(slots), dim3(256), 0, s, (const bf16_t*)big, (const bf16_t*)thin, dWp, db ? dbp : nullptr, rows_total, Cb, rps, big_is_dy),
-               hipLaunchKernelGGL(pw_wgrad_thin_kernel<float>, dim3(slots), dim3(256), 0, s, (const float*)big, (const float*)thin, dWp, db ? dbp : nullptr, rows_total, Cb, rps, big_is_dy),
-               "pw_wgrad")
+    PYTC_DISPATCH_DTYPE(dtype, "pw_wgrad", T,
+                        hipLaunchKernelGGL(pw_wgrad_thin_kernel<T>, dim3(slots), dim3(256), 0, s, (const T*)big, (const T*)thin, dWp, db ? dbp : nullptr, rows_total, Cb, rps, big_is_dy));
   } else {
     dim3 grid(slots, ((C_out + WG_TO - 1) / WG_TO) * ((C_in + WG_TK - 1) / WG_TK)), block(256);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(pw_wgrad_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)x, ab, (const bf16_t*)dy, dWp, db ? dbp : nullptr, rows_total, (long)rows_per_sample, C_in, C_out, rps, slots, x_act),
-               hipLaunchKernelGGL(pw_wgrad_kernel<float>, grid, block, 0, s, (const float*)x, ab, (const float*)dy, dWp, db ? dbp : nullptr, rows_total, (long)rows_per_sample, C_in, C_out, rps, slots, x_act),
-               "pw_wgrad")
+    PYTC_DISPATCH_DTYPE(dtype, "pw_wgrad", T,
+                        hipLaunchKernelGGL(pw_wgrad_kernel<T>, grid, block, 0, s, (const T*)x, ab, (const T*)dy, dWp, db ? dbp : nullptr, rows_total, (long)rows_per_sample, C_in, C_out, rps, slots, x_act));
   }
   const long nW = (long)C_out * C_in;
   if (slots_out) *slots_out = slots;
@@ -1958,8 +1946,7 @@ extern "C" int pytc_norm_bwd_apply(const void* dtn, const void* t, const float* 
                                    int s_parts, void* dt, int N, int64_t rows, int C, float count, int dtype,
                                    const int32_t* crop_grid, void* stream) {
   PYTC_REQUIRE(dtn && t && mean_rstd && s_in && s_parts >= 1 && dt && count > 0.f, "norm_bwd_apply: bad arguments");
-  const bool vec = dtype == PYTC_BF16 ? (C % 8 == 0) : (C % 4 == 0);
-  PYTC_REQUIRE(vec, "norm_bwd_apply: C must be a multiple of %d", dtype == PYTC_BF16 ? 8 : 4);
+  PYTC_REQUIRE(C % elems_per_16b(dtype) == 0, "norm_bwd_apply: C must be a multiple of %d", elems_per_16b(dtype));
   PYTC_REQUIRE(s_parts == 1 || C <= NORM_APPLY_MAX_PART_C, "norm_bwd_apply: statistics in parts need C <= %d", NORM_APPLY_MAX_PART_C);
   int ch = 0, cw = 0;
   if (crop_grid) {
@@ -1971,10 +1958,8 @@ extern "C" int pytc_norm_bwd_apply(const void* dtn, const void* t, const float* 
   const long rps = (rows + slots - 1) / slots;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(slots, N), block(256);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, gamma, s_in, 1.0f / count, (bf16_t*)dt, (long)rows, C, rps, ch, cw, s_parts),
-             hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<float>, grid, block, 0, s, (const float*)dtn, (const float*)t, mean_rstd, gamma, s_in, 1.0f / count, (float*)dt, (long)rows, C, rps, ch, cw, s_parts),
-             "norm_bwd_apply")
+  PYTC_DISPATCH_DTYPE(dtype, "norm_bwd_apply", T,
+                      hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<T>, grid, block, 0, s, (const T*)dtn, (const T*)t, mean_rstd, gamma, s_in, 1.0f / count, (T*)dt, (long)rows, C, rps, ch, cw, s_parts));
   PYTC_LAUNCH_CHECK("norm_bwd_apply");
   return PYTC_OK;
 }
@@ -1982,8 +1967,8 @@ extern "C" int pytc_norm_bwd_apply(const void* dtn, const void* t, const float* 
 // z-march form of the stride-1 3x3x3 case (dwconv_kernels.hip)
 namespace pytc {
 int dw_wgrad_march_slots(int N, int D, int H, int W, int C, int K, int stride, int dtype);
-void dw_wgrad_march_launch(const void* gr, const void* x, float* dWp, float* dbp, int N, int D, int H, int W, int C,
-                           int dtype, hipStream_t s);
+int dw_wgrad_march_launch(const void* gr, const void* x, float* dWp, float* dbp, int N, int D, int H, int W, int C,
+                          int dtype, hipStream_t s);
 }
 static int march_slots(int N, const int32_t* gd, const int32_t* xd, int C, int K, int stride, int dtype) {
   if (gd[0] != xd[0] || gd[1] != xd[1] || gd[2] != xd[2]) return 0;
@@ -1991,13 +1976,13 @@ static int march_slots(int N, const int32_t* gd, const int32_t* xd, int C, int K
 }
 
 static bool wg_vec_ok(int C, int K, int dtype) {
-  const int epv = dtype == PYTC_BF16 ? 8 : 4;
+  const int epv = elems_per_16b(dtype);
   return K == 3 && C % epv == 0 && C / epv <= 256 && tuning_get(K_dw_wgrad_vec) != 0;
 }
 static void make_wg_vec(DwWg& q, long& rps, int N, const int32_t* gd, const int32_t* xd, int C, int K, int stride, int dtype) {
   q.N = N; q.Dg = gd[0]; q.Hg = gd[1]; q.Wg = gd[2]; q.Dx = xd[0]; q.Hx = xd[1]; q.Wx = xd[2];
   q.C = C; q.K = K; q.stride = stride; q.pad = K / 2; q.lpv = q.vs = q.iters = 0;
-  const int PL = 256 / (C / (dtype == PYTC_BF16 ? 8 : 4));
+  const int PL = 256 / (C / elems_per_16b(dtype));
   const long vg = (long)q.Dg * q.Hg * q.Wg;
   // positions per lane: 16 where that still gives the chip >= 1024 workgroups, down to 4 below (a 14^3 x 256 launch had 264 workgroups whose
   // lanes walked 16 positions, one L2 round trip each: 50 us for 11 MB)
@@ -2009,7 +1994,7 @@ static void make_wg_vec(DwWg& q, long& rps, int N, const int32_t* gd, const int3
 }
 
 static bool make_wg(DwWg& q, int N, const int32_t* gd, const int32_t* xd, int C, int K, int stride, int dtype, int& vec) {
-  int maxv = dtype == PYTC_BF16 ? 4 : 2;
+  int maxv = elems_per_16b(dtype) / 2;             // 8-byte vectors
   vec = 0;
   for (int v = maxv; v >= 1; v >>= 1)
     if (C % v == 0 && C / v <= 256) { vec = v; break; }
@@ -2050,13 +2035,14 @@ static int dw_wgrad_impl(const void* g, const void* x, float* dW, float* db, flo
                          const int32_t* gdims, const int32_t* xdims, int C, int K, int stride, int dtype,
                          void* stream, bool reduce, int* slots_out) {
   PYTC_REQUIRE(g && x && (dW || !reduce) && workspace && gdims && xdims, "dw_wgrad: null pointer");
+  PYTC_CHECK_DTYPE(dtype, "dw_wgrad");
   const int ms = march_slots(N, gdims, xdims, C, K, stride, dtype);
   if (ms > 0) {
     const long nWm = 27L * C;
     float* dWm = workspace;
     float* dbm = workspace + (long)ms * nWm;
     hipStream_t sm = (hipStream_t)stream;
-    dw_wgrad_march_launch(g, x, dWm, db ? dbm : nullptr, N, gdims[0], gdims[1], gdims[2], C, dtype, sm);
+    if (int st = dw_wgrad_march_launch(g, x, dWm, db ? dbm : nullptr, N, gdims[0], gdims[1], gdims[2], C, dtype, sm)) return st;
     if (slots_out) *slots_out = ms;
     if (reduce) reduce_slots_pair(dWm, dW, nWm, dbm, db, (long)C, ms, sm);
     PYTC_LAUNCH_CHECK("dw_wgrad");
@@ -2073,10 +2059,8 @@ static int dw_wgrad_impl(const void* g, const void* x, float* dW, float* db, flo
     hipStream_t sv = (hipStream_t)stream;
     q.kz_inner = 1;
     dim3 grid((unsigned)(q.slots * N * 3), 1, 1), block(256);
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(dw_wgrad_vec_kernel<bf16_t>, grid, block, 0, sv, (const bf16_t*)g, (const bf16_t*)x, dWv, db ? dbv : nullptr, q, rps),
-               hipLaunchKernelGGL(dw_wgrad_vec_kernel<float>, grid, block, 0, sv, (const float*)g, (const float*)x, dWv, db ? dbv : nullptr, q, rps),
-               "dw_wgrad")
+    PYTC_DISPATCH_DTYPE(dtype, "dw_wgrad", T,
+                        hipLaunchKernelGGL(dw_wgrad_vec_kernel<T>, grid, block, 0, sv, (const T*)g, (const T*)x, dWv, db ? dbv : nullptr, q, rps));
     if (slots_out) *slots_out = total;
     if (reduce) reduce_slots_pair(dWv, dW, nWv, dbv, db, (long)C, total, sv);
     PYTC_LAUNCH_CHECK("dw_wgrad");
@@ -2089,10 +2073,11 @@ static int dw_wgrad_impl(const void* g, const void* x, float* dW, float* db, flo
   float* dWp = workspace;
   float* dbp = workspace + (long)total_slots * nW;
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (dtype == PYTC_BF16) rc = vec == 4 ? launch_dwwg<bf16_t, 4>(g, x, dWp, dbp, q, s) : vec == 2 ? launch_dwwg<bf16_t, 2>(g, x, dWp, dbp, q, s) : launch_dwwg<bf16_t, 1>(g, x, dWp, dbp, q, s);
-  else rc = vec == 2 ? launch_dwwg<float, 2>(g, x, dWp, dbp, q, s) : launch_dwwg<float, 1>(g, x, dWp, dbp, q, s);
-  if (rc != PYTC_OK) return rc;
+  PYTC_DISPATCH_DTYPE(dtype, "dw_wgrad", T,
+    constexpr int V8 = elems_per_16b_of<T> / 2;      // make_wg's widest
+    if (int rc = vec == V8 ? launch_dwwg<T, V8>(g, x, dWp, dbp, q, s) : vec == 2 ? launch_dwwg<T, 2>(g, x, dWp, dbp, q, s)
+                                                                                  : launch_dwwg<T, 1>(g, x, dWp, dbp, q, s))
+      return rc);
   if (slots_out) *slots_out = total_slots;
   if (reduce) reduce_slots_pair(dWp, dW, nW, dbp, db, (long)C, total_slots, s);
   PYTC_LAUNCH_CHECK("dw_wgrad");
@@ -2122,32 +2107,16 @@ extern "C" int pytc_norm_bwd(const void* dtn, const void* t, const float* mean_r
   size_t lds = (size_t)(256 / Cw) * 2 * Cw * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(slots, N), block(256);
-  const bool vec = dtype == PYTC_BF16 ? (C % 8 == 0) : (C % 4 == 0);
-  if (vec) {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((colstats_kernel<bf16_t, 1>), grid, block, 0, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               hipLaunchKernelGGL((colstats_kernel<float, 1>), grid, block, 0, s, (const float*)dtn, (const float*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               "norm_bwd")
-  } else {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(norm_bwd_stats_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               hipLaunchKernelGGL(norm_bwd_stats_kernel<float>, grid, block, lds, s, (const float*)dtn, (const float*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               "norm_bwd")
-  }
+  const bool vec = C % elems_per_16b(dtype) == 0;
+  PYTC_DISPATCH_DTYPE(dtype, "norm_bwd", T,
+    if (vec) hipLaunchKernelGGL((colstats_kernel<T, 1>), grid, block, 0, s, (const T*)dtn, (const T*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps);
+    else hipLaunchKernelGGL(norm_bwd_stats_kernel<T>, grid, block, lds, s, (const T*)dtn, (const T*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps));
   // reduce slots per sample: stats_ws [N][slots][2][C] -> s_out [N][2][C]
   hipLaunchKernelGGL(reduce_slots_batched_kernel, dim3(ceil_div(2L * C, 16), N), dim3(256), 0, s, stats_ws, s_out, 2L * C, slots);
   const long total = (long)N * rows * C;
-  if (vec) {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, gamma, s_out, 1.0f / count, (bf16_t*)dt, (long)rows, C, rps),
-               hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<float>, grid, block, 0, s, (const float*)dtn, (const float*)t, mean_rstd, gamma, s_out, 1.0f / count, (float*)dt, (long)rows, C, rps),
-               "norm_bwd")
-  } else {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(norm_bwd_apply_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, gamma, s_out, 1.0f / count, (bf16_t*)dt, (long)rows, C, total),
-               hipLaunchKernelGGL(norm_bwd_apply_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)dtn, (const float*)t, mean_rstd, gamma, s_out, 1.0f / count, (float*)dt, (long)rows, C, total),
-               "norm_bwd")
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "norm_bwd", T,
+    if (vec) hipLaunchKernelGGL(norm_bwd_apply_vec_kernel<T>, grid, block, 0, s, (const T*)dtn, (const T*)t, mean_rstd, gamma, s_out, 1.0f / count, (T*)dt, (long)rows, C, rps);
+    else hipLaunchKernelGGL(norm_bwd_apply_kernel<T>, dim3(grid_for(total)), dim3(256), 0, s, (const T*)dtn, (const T*)t, mean_rstd, gamma, s_out, 1.0f / count, (T*)dt, (long)rows, C, total));
   PYTC_LAUNCH_CHECK("norm_bwd");
   return PYTC_OK;
 }
@@ -2162,18 +2131,10 @@ extern "C" int pytc_norm_bwd_stats(const void* dtn, const void* t, const float* 
   size_t lds = (size_t)(256 / Cw) * 2 * Cw * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(slots, N), block(256);
-  const bool vec = dtype == PYTC_BF16 ? (C % 8 == 0) : (C % 4 == 0);
-  if (vec) {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL((colstats_kernel<bf16_t, 1>), grid, block, 0, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               hipLaunchKernelGGL((colstats_kernel<float, 1>), grid, block, 0, s, (const float*)dtn, (const float*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               "norm_bwd_stats")
-  } else {
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(norm_bwd_stats_kernel<bf16_t>, grid, block, lds, s, (const bf16_t*)dtn, (const bf16_t*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               hipLaunchKernelGGL(norm_bwd_stats_kernel<float>, grid, block, lds, s, (const float*)dtn, (const float*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps),
-               "norm_bwd_stats")
-  }
+  const bool vec = C % elems_per_16b(dtype) == 0;
+  PYTC_DISPATCH_DTYPE(dtype, "norm_bwd_stats", T,
+    if (vec) hipLaunchKernelGGL((colstats_kernel<T, 1>), grid, block, 0, s, (const T*)dtn, (const T*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps);
+    else hipLaunchKernelGGL(norm_bwd_stats_kernel<T>, grid, block, lds, s, (const T*)dtn, (const T*)t, mean_rstd, stats_ws, (long)rows, C, slots, rps));
   hipLaunchKernelGGL(reduce_slots_batched_kernel, dim3(ceil_div(2L * C, 16), N), dim3(256), 0, s, stats_ws, s_out, 2L * C, slots);
   PYTC_LAUNCH_CHECK("norm_bwd_stats");
   return PYTC_OK;
@@ -2195,7 +2156,7 @@ extern "C" int pytc_dwconv3d_bwd_data(const void* dy, const float* w, void* dx, 
 /* dx = conv^T(dy) + addend (addend shaped like dx; 16-byte channel groups only) */
 extern "C" int pytc_dwconv3d_bwd_data_add(const void* dy, const float* w, const void* addend, void* dx, int N, const int32_t* xdims,
                                           const int32_t* ydims, int C, int K, int stride, int dtype, void* stream) {
-  PYTC_REQUIRE(addend && C % (dtype == PYTC_BF16 ? 8 : 4) == 0, "dwconv3d_bwd_data_add: addend and 16-byte channel groups required (C = %d)", C);
+  PYTC_REQUIRE(addend && C % elems_per_16b(dtype) == 0, "dwconv3d_bwd_data_add: addend and 16-byte channel groups required (C = %d)", C);
   return dwconv3d_bwd_data_impl(dy, w, addend, dx, N, xdims, ydims, C, K, stride, dtype, stream);
 }
 
@@ -2207,20 +2168,16 @@ static int dwconv3d_bwd_data_impl(const void* dy, const float* w, const void* ad
   g.C = C; g.K = K; g.stride = stride; g.pad = K / 2;
   const long total = (long)N * g.D * g.H * g.W * C;
   hipStream_t s = (hipStream_t)stream;
-  const int epv = dtype == PYTC_BF16 ? 8 : 4;
+  const int epv = elems_per_16b(dtype);
   if (C % epv == 0) {
     const long tv = total / epv;
-    DISPATCH_T(dtype,
-               hipLaunchKernelGGL(dwconv_bwd_data_vec_kernel<bf16_t>, dim3(ceil_div(tv, 256)), dim3(256), 0, s, (const bf16_t*)dy, w, (bf16_t*)dx, g, tv, (const bf16_t*)addend),
-               hipLaunchKernelGGL(dwconv_bwd_data_vec_kernel<float>, dim3(ceil_div(tv, 256)), dim3(256), 0, s, (const float*)dy, w, (float*)dx, g, tv, (const float*)addend),
-               "dwconv3d_bwd_data")
+    PYTC_DISPATCH_DTYPE(dtype, "dwconv3d_bwd_data", T,
+                        hipLaunchKernelGGL(dwconv_bwd_data_vec_kernel<T>, dim3(ceil_div(tv, 256)), dim3(256), 0, s, (const T*)dy, w, (T*)dx, g, tv, (const T*)addend));
     PYTC_LAUNCH_CHECK("dwconv3d_bwd_data");
     return PYTC_OK;
   }
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(dwconv_bwd_data_kernel<bf16_t>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const bf16_t*)dy, w, (bf16_t*)dx, g, total),
-             hipLaunchKernelGGL(dwconv_bwd_data_kernel<float>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const float*)dy, w, (float*)dx, g, total),
-             "dwconv3d_bwd_data")
+  PYTC_DISPATCH_DTYPE(dtype, "dwconv3d_bwd_data", T,
+                      hipLaunchKernelGGL(dwconv_bwd_data_kernel<T>, dim3(ceil_div(total, 256)), dim3(256), 0, s, (const T*)dy, w, (T*)dx, g, total));
   PYTC_LAUNCH_CHECK("dwconv3d_bwd_data");
   return PYTC_OK;
 }

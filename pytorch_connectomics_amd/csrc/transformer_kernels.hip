@@ -699,14 +699,13 @@ extern "C" int pytc_linear_fwd(const void* x, const float* w, const float* bias,
   PYTC_REQUIRE(x && w && y && M >= 1 && N >= 1 && K >= 1, "linear_fwd: bad arguments");
   PYTC_REQUIRE(!pos || (pos_rows >= 1 && M % pos_rows == 0), "linear_fwd: %d rows are not a whole number of %d-row position blocks",
                M, pos_rows);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "linear_fwd: bad dtype");
+  PYTC_CHECK_DTYPE(dtype, "linear_fwd");
   LinParams p;
   memset(&p, 0, sizeof(p));
   p.A = x; p.B = w; p.C = y; p.bias = bias; p.pos = pos; p.P = pos ? pos_rows : 1; p.res = res; p.gelu_a = x_gelu;
   p.M = M; p.N = N; p.K = K; p.lda = K; p.ldb = K; p.ldc = N;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) linear_launch<bf16_t, float, bf16_t, false, true>(p, st);
-  else linear_launch<float, float, float, false, true>(p, st);
+  PYTC_DISPATCH_DTYPE(dtype, "linear_fwd", T, linear_launch<T, float, T, false, true>(p, st));
   PYTC_LAUNCH_CHECK("linear_fwd");
   return PYTC_OK;
 }
@@ -714,15 +713,14 @@ extern "C" int pytc_linear_fwd(const void* x, const float* w, const float* bias,
 extern "C" int pytc_linear_bwd_data(const void* dy, const float* w, const void* x_gelu, void* dx, int M, int N, int K, int dtype,
                                     void* stream) {
   PYTC_REQUIRE(dy && w && dx && M >= 1 && N >= 1 && K >= 1, "linear_bwd_data: bad arguments");
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "linear_bwd_data: bad dtype");
+  PYTC_CHECK_DTYPE(dtype, "linear_bwd_data");
   LinParams p;
   memset(&p, 0, sizeof(p));
   // dx[M][K] = dy[M][N] . w[N][K]: the GEMM's (M, N, K) are (M, K, N)
   p.A = dy; p.B = w; p.C = dx; p.M = M; p.N = K; p.K = N; p.lda = N; p.ldb = K; p.ldc = K; p.P = 1;
   p.res = x_gelu; p.res_gelu_bwd = x_gelu ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) linear_launch<bf16_t, float, bf16_t, false, false>(p, st);
-  else linear_launch<float, float, float, false, false>(p, st);
+  PYTC_DISPATCH_DTYPE(dtype, "linear_bwd_data", T, linear_launch<T, float, T, false, false>(p, st));
   PYTC_LAUNCH_CHECK("linear_bwd_data");
   return PYTC_OK;
 }
@@ -731,7 +729,7 @@ extern "C" int pytc_linear_wgrad(const void* dy, const void* x, float* dw, float
                                  int x_gelu, int dtype, void* stream) {
   PYTC_REQUIRE(dy && x && M >= 1 && N >= 1 && K >= 1, "linear_wgrad: bad arguments");
   PYTC_REQUIRE(!dpos || (pos_rows >= 1 && M % pos_rows == 0), "linear_wgrad: bad position-block rows %d", pos_rows);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "linear_wgrad: bad dtype");
+  PYTC_CHECK_DTYPE(dtype, "linear_wgrad");
   hipStream_t st = (hipStream_t)stream;
   if (dw) {
     // dw[N][K] = sum_m dy[m][n] x[m][k]: A(n, m) = dy[m][n] (transposed), B(m, k) = x[m][k]; one thread owns each output, K = M
@@ -739,20 +737,13 @@ extern "C" int pytc_linear_wgrad(const void* dy, const void* x, float* dw, float
     LinParams p;
     memset(&p, 0, sizeof(p));
     p.A = dy; p.B = x; p.C = dw; p.M = N; p.N = K; p.K = M; p.lda = N; p.ldb = K; p.ldc = K; p.P = 1; p.gelu_b = x_gelu;
-    if (dtype == PYTC_BF16) linear_launch<bf16_t, bf16_t, float, true, false>(p, st);
-    else linear_launch<float, float, float, true, false>(p, st);
+    PYTC_DISPATCH_DTYPE(dtype, "linear_wgrad", T, linear_launch<T, T, float, true, false>(p, st));
   }
   const int blk = 256;
-  if (db) {
-    if (dtype == PYTC_BF16) hipLaunchKernelGGL(colsum_period_kernel<bf16_t>, dim3(ceil_div(N, blk)), dim3(blk), 0, st, (const bf16_t*)dy, db, M, N, 1);
-    else hipLaunchKernelGGL(colsum_period_kernel<float>, dim3(ceil_div(N, blk)), dim3(blk), 0, st, (const float*)dy, db, M, N, 1);
-  }
-  if (dpos) {
-    const long n = (long)pos_rows * N;
-    if (dtype == PYTC_BF16)
-      hipLaunchKernelGGL(colsum_period_kernel<bf16_t>, dim3(ceil_div(n, blk)), dim3(blk), 0, st, (const bf16_t*)dy, dpos, M, N, pos_rows);
-    else hipLaunchKernelGGL(colsum_period_kernel<float>, dim3(ceil_div(n, blk)), dim3(blk), 0, st, (const float*)dy, dpos, M, N, pos_rows);
-  }
+  const long n = (long)pos_rows * N;
+  PYTC_DISPATCH_DTYPE(dtype, "linear_wgrad", T,
+    if (db) hipLaunchKernelGGL(colsum_period_kernel<T>, dim3(ceil_div(N, blk)), dim3(blk), 0, st, (const T*)dy, db, M, N, 1);
+    if (dpos) hipLaunchKernelGGL(colsum_period_kernel<T>, dim3(ceil_div(n, blk)), dim3(blk), 0, st, (const T*)dy, dpos, M, N, pos_rows));
   PYTC_LAUNCH_CHECK("linear_wgrad");
   return PYTC_OK;
 }
@@ -760,7 +751,7 @@ extern "C" int pytc_linear_wgrad(const void* dy, const void* x, float* dw, float
 static int ln_wide_check(const char* what, int64_t rows, int C, int dtype) {
   PYTC_REQUIRE(rows >= 1 && C >= 64 && C <= 64 * LN_MAXV && C % 64 == 0, "%s: C = %d must be a multiple of 64 in [64, %d]", what, C,
                64 * LN_MAXV);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   return PYTC_OK;
 }
 
@@ -770,9 +761,8 @@ extern "C" int pytc_layernorm_wide(const void* x, void* y, const float* gamma, c
   PYTC_REQUIRE(x && y && gamma && beta, "layernorm_wide: null pointer");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(layernorm_wide_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, gamma, beta, (long)rows, C, eps);
-  else hipLaunchKernelGGL(layernorm_wide_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (float*)y, gamma, beta, (long)rows, C, eps);
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_wide", T,
+                      hipLaunchKernelGGL(layernorm_wide_fwd_kernel<T>, grid, dim3(256), 0, st, (const T*)x, (T*)y, gamma, beta, (long)rows, C, eps));
   PYTC_LAUNCH_CHECK("layernorm_wide");
   return PYTC_OK;
 }
@@ -785,12 +775,9 @@ extern "C" int pytc_layernorm_wide_bwd(const void* dy, const void* x, const floa
   PYTC_REQUIRE(dy && x && gamma && dx && partial, "layernorm_wide_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int slots = ceil_div(rows, LN_ROWS_PER_BLOCK);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(layernorm_wide_bwd_kernel<bf16_t>, dim3(slots), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, gamma,
-                       (bf16_t*)dx, partial, (long)rows, C, eps);
-  else
-    hipLaunchKernelGGL(layernorm_wide_bwd_kernel<float>, dim3(slots), dim3(256), 0, st, (const float*)dy, (const float*)x, gamma,
-                       (float*)dx, partial, (long)rows, C, eps);
+  PYTC_DISPATCH_DTYPE(dtype, "layernorm_wide_bwd", T,
+                      hipLaunchKernelGGL(layernorm_wide_bwd_kernel<T>, dim3(slots), dim3(256), 0, st, (const T*)dy, (const T*)x, gamma, (T*)dx,
+                                         partial, (long)rows, C, eps));
   if (dgamma || dbeta)
     hipLaunchKernelGGL(layernorm_wide_reduce_kernel, dim3(ceil_div(2 * C, 256)), dim3(256), 0, st, (const float*)partial, dgamma, dbeta,
                        slots, C);
@@ -801,13 +788,11 @@ extern "C" int pytc_layernorm_wide_bwd(const void* dy, const void* x, const floa
 extern "C" int pytc_patch_gather16(const void* src, void* dst, int B, int D, int H, int W, int C, int scatter, int dtype, void* stream) {
   PYTC_REQUIRE(src && dst && B >= 1 && C >= 1 && D >= 16 && H >= 16 && W >= 16 && D % 16 == 0 && H % 16 == 0 && W % 16 == 0,
                "patch_gather16: grid (%d, %d, %d) is not a whole number of 16^3 patches", D, H, W);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "patch_gather16: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   const long total = (long)B * D * H * W * C;
   const int grid = (int)std::min<long>((total + 255) / 256, 16384);
-  if (dtype == PYTC_BF16)
-    hipLaunchKernelGGL(patch_gather_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, B, D, H, W, C, scatter);
-  else hipLaunchKernelGGL(patch_gather_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)src, (float*)dst, B, D, H, W, C, scatter);
+  PYTC_DISPATCH_DTYPE(dtype, "patch_gather16", T,
+                      hipLaunchKernelGGL(patch_gather_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)src, (T*)dst, B, D, H, W, C, scatter));
   PYTC_LAUNCH_CHECK("patch_gather16");
   return PYTC_OK;
 }
@@ -817,7 +802,7 @@ extern "C" int pytc_attention_supported(int d_head) { return d_head == 32 || d_h
 static int attn_check(const char* what, int B, int N, int heads, int d_head, int dtype) {
   PYTC_REQUIRE(B >= 1 && N >= 1 && heads >= 1, "%s: bad sizes", what);
   PYTC_REQUIRE(pytc_attention_supported(d_head), "%s: head width %d has no kernel (32, 64)", what, d_head);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   return PYTC_OK;
 }
 
@@ -835,13 +820,9 @@ extern "C" int pytc_attention_fwd(const void* qkv, void* out, float* lse, int B,
   if (int s = attn_check("attention_fwd", B, N, heads, d_head, dtype)) return s;
   PYTC_REQUIRE(qkv && out && lse, "attention_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) {
-    if (d_head == 64) attn_fwd_launch<bf16_t, 64>(qkv, out, lse, B, N, heads, scale, st);
-    else attn_fwd_launch<bf16_t, 32>(qkv, out, lse, B, N, heads, scale, st);
-  } else {
-    if (d_head == 64) attn_fwd_launch<float, 64>(qkv, out, lse, B, N, heads, scale, st);
-    else attn_fwd_launch<float, 32>(qkv, out, lse, B, N, heads, scale, st);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "attention_fwd", T,
+                      if (d_head == 64) attn_fwd_launch<T, 64>(qkv, out, lse, B, N, heads, scale, st);
+                      else attn_fwd_launch<T, 32>(qkv, out, lse, B, N, heads, scale, st));
   PYTC_LAUNCH_CHECK("attention_fwd");
   return PYTC_OK;
 }
@@ -868,13 +849,9 @@ extern "C" int pytc_attention_bwd(const void* qkv, const void* out, const void* 
   if (int s = attn_check("attention_bwd", B, N, heads, d_head, dtype)) return s;
   PYTC_REQUIRE(qkv && out && dout && lse && dvec && dqkv, "attention_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) {
-    if (d_head == 64) attn_bwd_launch<bf16_t, 64>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
-    else attn_bwd_launch<bf16_t, 32>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
-  } else {
-    if (d_head == 64) attn_bwd_launch<float, 64>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
-    else attn_bwd_launch<float, 32>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "attention_bwd", T,
+                      if (d_head == 64) attn_bwd_launch<T, 64>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st);
+                      else attn_bwd_launch<T, 32>(qkv, out, dout, lse, dvec, dqkv, B, N, heads, scale, st));
   PYTC_LAUNCH_CHECK("attention_bwd");
   return PYTC_OK;
 }
@@ -893,7 +870,7 @@ static int win_args(const char* what, const float* table, const int* geom, int n
                     WinArgs* wa) {
   PYTC_REQUIRE(table && geom && nwin >= 1 && heads >= 1, "%s: bad arguments", what);
   PYTC_REQUIRE(pytc_window_attention_supported(d_head), "%s: head width %d has no kernel (16, 32)", what, d_head);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   memset(wa, 0, sizeof(*wa));
   wa->table = table;
   int per_img = 1, n = 1;
@@ -930,13 +907,9 @@ extern "C" int pytc_window_attention_fwd(const void* qkv, const float* table, co
   if (int s = win_args("window_attention_fwd", table, geom, nwin, N, heads, d_head, dtype, &wa)) return s;
   PYTC_REQUIRE(qkv && out && lse, "window_attention_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) {
-    if (d_head == 16) win_fwd_launch<bf16_t, 16>(qkv, out, lse, nwin, N, heads, scale, wa, st);
-    else win_fwd_launch<bf16_t, 32>(qkv, out, lse, nwin, N, heads, scale, wa, st);
-  } else {
-    if (d_head == 16) win_fwd_launch<float, 16>(qkv, out, lse, nwin, N, heads, scale, wa, st);
-    else win_fwd_launch<float, 32>(qkv, out, lse, nwin, N, heads, scale, wa, st);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "window_attention_fwd", T,
+                      if (d_head == 16) win_fwd_launch<T, 16>(qkv, out, lse, nwin, N, heads, scale, wa, st);
+                      else win_fwd_launch<T, 32>(qkv, out, lse, nwin, N, heads, scale, wa, st));
   PYTC_LAUNCH_CHECK("window_attention_fwd");
   return PYTC_OK;
 }
@@ -975,13 +948,9 @@ extern "C" int pytc_window_attention_bwd(const void* qkv, const float* table, co
   if (int s = win_args("window_attention_bwd", table, geom, nwin, N, heads, d_head, dtype, &wa)) return s;
   PYTC_REQUIRE(qkv && out && dout && lse && dvec && dqkv && (!dtable || partial), "window_attention_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PYTC_BF16) {
-    if (d_head == 16) win_bwd_launch<bf16_t, 16>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
-    else win_bwd_launch<bf16_t, 32>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
-  } else {
-    if (d_head == 16) win_bwd_launch<float, 16>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
-    else win_bwd_launch<float, 32>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "window_attention_bwd", T,
+                      if (d_head == 16) win_bwd_launch<T, 16>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st);
+                      else win_bwd_launch<T, 32>(qkv, out, dout, lse, dvec, dqkv, partial, dtable, nwin, N, heads, scale, wa, st));
   PYTC_LAUNCH_CHECK("window_attention_bwd");
   return PYTC_OK;
 }

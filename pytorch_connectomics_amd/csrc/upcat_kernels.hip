@@ -273,7 +273,7 @@ static int upcat_check(const char* what, int N, int d, int h, int w, int D, int 
   PYTC_REQUIRE((D == 2 * d || D == 2 * d + 1) && (H == 2 * h || H == 2 * h + 1) && (W == 2 * w || W == 2 * w + 1),
                "%s: skip grid (%d, %d, %d) is neither twice nor twice + 1 the low grid (%d, %d, %d)", what, D, H, W, d, h, w);
   PYTC_REQUIRE((long)N * D * H * W < (1L << 31), "%s: too many voxels for 32-bit voxel indices", what);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   return PYTC_OK;
 }
 
@@ -303,13 +303,9 @@ extern "C" int pytc_upcat_deconv2_fwd(const void* x_low, const float* w, const f
   hipStream_t st = (hipStream_t)stream;
   const long vox = (long)N * D * H * W;
   dim3 grid(ceil_div(8L * C_u, UP_BP), ceil_div(p.rows, UP_BQ));
-  if (dtype == PYTC_BF16) {
-    upcat_copy<bf16_t>(x_e, cat, vox, C_e, C_e, 0, C_e + C_u, 0, st);
-    hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_FWD>), grid, dim3(256), 0, st, p);
-  } else {
-    upcat_copy<float>(x_e, cat, vox, C_e, C_e, 0, C_e + C_u, 0, st);
-    hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_FWD>), grid, dim3(256), 0, st, p);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "upcat_deconv2_fwd", T,
+                      upcat_copy<T>(x_e, cat, vox, C_e, C_e, 0, C_e + C_u, 0, st);
+                      hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_FWD>), grid, dim3(256), 0, st, p));
   PYTC_LAUNCH_CHECK("upcat_deconv2_fwd");
   return PYTC_OK;
 }
@@ -323,13 +319,9 @@ extern "C" int pytc_upcat_deconv2_bwd_data(const void* dcat, const float* w, voi
   hipStream_t st = (hipStream_t)stream;
   const long vox = (long)N * D * H * W;
   dim3 grid(ceil_div(C_in, UP_BP), ceil_div(p.rows, UP_BQ));
-  if (dtype == PYTC_BF16) {
-    if (dx_e) upcat_copy<bf16_t>(dcat, dx_e, vox, C_e, C_e + C_u, 0, C_e, 0, st);
-    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
-  } else {
-    if (dx_e) upcat_copy<float>(dcat, dx_e, vox, C_e, C_e + C_u, 0, C_e, 0, st);
-    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "upcat_deconv2_bwd_data", T,
+                      if (dx_e) upcat_copy<T>(dcat, dx_e, vox, C_e, C_e + C_u, 0, C_e, 0, st);
+                      if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_DGRAD>), grid, dim3(256), 0, st, p));
   PYTC_LAUNCH_CHECK("upcat_deconv2_bwd_data");
   return PYTC_OK;
 }
@@ -343,7 +335,7 @@ static int upcat_wgrad_splits(int rows, int C_in, int C_u, int ks) {
 }
 
 extern "C" int64_t pytc_upcat_deconv2_wgrad_ws_elems(int rows, int C_in, int C_u, int dtype) {
-  const int ks = dtype == PYTC_BF16 ? Mma<bf16_t>::KSTEP : Mma<float>::KSTEP;
+  const int ks = mfma_kstep(dtype);
   return (int64_t)upcat_wgrad_splits(rows, C_in, C_u, ks) * (C_in + 1) * 8 * C_u;
 }
 
@@ -353,14 +345,13 @@ extern "C" int pytc_upcat_deconv2_wgrad(const void* x_low, const void* dcat, flo
   PYTC_REQUIRE(x_low && dcat && workspace && dw, "upcat_deconv2_wgrad: null pointer");
   UpcatParams p = upcat_params(N, d, h, wd, D, H, W, C_in, C_e, C_u);
   p.x_low = x_low; p.dcat = dcat; p.out = workspace;
-  const int ks = dtype == PYTC_BF16 ? Mma<bf16_t>::KSTEP : Mma<float>::KSTEP;
+  const int ks = mfma_kstep(dtype);
   const int S = upcat_wgrad_splits(p.rows, C_in, C_u, ks);
   p.rows_per_split = ceil_div(ceil_div(p.rows, S), ks) * ks;
   const int S_used = ceil_div(p.rows, p.rows_per_split);     // every split the reduction reads is written (the last may be short)
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(C_in + 1, UP_BP), ceil_div(8L * C_u, UP_BQ), S_used);
-  if (dtype == PYTC_BF16) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
+  PYTC_DISPATCH_DTYPE(dtype, "upcat_deconv2_wgrad", T, hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_WGRAD>), grid, dim3(256), 0, st, p));
   const long n = (long)C_in * 8 * C_u + C_u;
   hipLaunchKernelGGL(upcat_wgrad_reduce_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const float*)workspace, dw, db, S_used,
                      C_in, C_u);
@@ -374,7 +365,7 @@ extern "C" int pytc_upcat_deconv2_wgrad(const void* x_low, const void* dcat, flo
 static int upfirst_check(const char* what, int N, int d, int h, int w, int C_in, int C_e, int C_u, int dtype) {
   PYTC_REQUIRE(N >= 1 && d >= 1 && h >= 1 && w >= 1 && C_in >= 1 && C_e >= 0 && C_u >= 1, "%s: bad sizes", what);
   PYTC_REQUIRE((long)N * 8 * d * h * w < (1L << 31), "%s: too many voxels for 32-bit voxel indices", what);
-  PYTC_REQUIRE(dtype == PYTC_BF16 || dtype == PYTC_F32, "%s: bad dtype", what);
+  PYTC_CHECK_DTYPE(dtype, what);
   return PYTC_OK;
 }
 
@@ -393,13 +384,9 @@ extern "C" int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const
   hipStream_t st = (hipStream_t)stream;
   const long vox = 8L * N * d * h * wd;
   dim3 grid(ceil_div(8L * C_u, UP_BP), ceil_div(p.rows, UP_BQ));
-  if (dtype == PYTC_BF16) {
-    if (C_e) upcat_copy<bf16_t>(x_e, out, vox, C_e, C_e, 0, C_e + C_u, C_u, st);
-    hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_FWD>), grid, dim3(256), 0, st, p);
-  } else {
-    if (C_e) upcat_copy<float>(x_e, out, vox, C_e, C_e, 0, C_e + C_u, C_u, st);
-    hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_FWD>), grid, dim3(256), 0, st, p);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "deconv2_upfirst_fwd", T,
+                      if (C_e) upcat_copy<T>(x_e, out, vox, C_e, C_e, 0, C_e + C_u, C_u, st);
+                      hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_FWD>), grid, dim3(256), 0, st, p));
   PYTC_LAUNCH_CHECK("deconv2_upfirst_fwd");
   return PYTC_OK;
 }
@@ -413,13 +400,9 @@ extern "C" int pytc_deconv2_upfirst_bwd_data(const void* dout, const float* w, v
   hipStream_t st = (hipStream_t)stream;
   const long vox = 8L * N * d * h * wd;
   dim3 grid(ceil_div(C_in, UP_BP), ceil_div(p.rows, UP_BQ));
-  if (dtype == PYTC_BF16) {
-    if (dx_e && C_e) upcat_copy<bf16_t>(dout, dx_e, vox, C_e, C_e + C_u, C_u, C_e, 0, st);
-    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
-  } else {
-    if (dx_e && C_e) upcat_copy<float>(dout, dx_e, vox, C_e, C_e + C_u, C_u, C_e, 0, st);
-    if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_DGRAD>), grid, dim3(256), 0, st, p);
-  }
+  PYTC_DISPATCH_DTYPE(dtype, "deconv2_upfirst_bwd_data", T,
+                      if (dx_e && C_e) upcat_copy<T>(dout, dx_e, vox, C_e, C_e + C_u, C_u, C_e, 0, st);
+                      if (dx_low) hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_DGRAD>), grid, dim3(256), 0, st, p));
   PYTC_LAUNCH_CHECK("deconv2_upfirst_bwd_data");
   return PYTC_OK;
 }
@@ -430,14 +413,13 @@ extern "C" int pytc_deconv2_upfirst_wgrad(const void* x_low, const void* dout, f
   PYTC_REQUIRE(x_low && dout && workspace && dw, "deconv2_upfirst_wgrad: null pointer");
   UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
   p.x_low = x_low; p.dcat = dout; p.out = workspace;
-  const int ks = dtype == PYTC_BF16 ? Mma<bf16_t>::KSTEP : Mma<float>::KSTEP;
+  const int ks = mfma_kstep(dtype);
   const int S = upcat_wgrad_splits(p.rows, C_in, C_u, ks);
   p.rows_per_split = ceil_div(ceil_div(p.rows, S), ks) * ks;
   const int S_used = ceil_div(p.rows, p.rows_per_split);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(C_in + 1, UP_BP), ceil_div(8L * C_u, UP_BQ), S_used);
-  if (dtype == PYTC_BF16) hipLaunchKernelGGL((upcat_gemm_kernel<bf16_t, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((upcat_gemm_kernel<float, UPCAT_WGRAD>), grid, dim3(256), 0, st, p);
+  PYTC_DISPATCH_DTYPE(dtype, "deconv2_upfirst_wgrad", T, hipLaunchKernelGGL((upcat_gemm_kernel<T, UPCAT_WGRAD>), grid, dim3(256), 0, st, p));
   const long n = (long)C_in * 8 * C_u + C_u;
   hipLaunchKernelGGL(upcat_wgrad_reduce_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, (const float*)workspace, dw, db, S_used,
                      C_in, C_u);

@@ -378,14 +378,9 @@ extern "C" int pytc_gather_windows(const float* vol, int C, int Z, int Y, int X,
   long per_win = (long)rz * ry * rx;
   dim3 grid(ceil_div(per_win, 256), 1, B), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (out_dtype == PYTC_F32)
-    hipLaunchKernelGGL(gather_windows_kernel<float>, grid, block, 0, s, vol, C, Z, Y, X, st, rz, ry, rx, view,
-                       pad_mode, cval, 0, 0, 0, (float*)out);
-  else if (out_dtype == PYTC_BF16)
-    hipLaunchKernelGGL(gather_windows_kernel<bf16_t>, grid, block, 0, s, vol, C, Z, Y, X, st, rz, ry, rx, view,
-                       pad_mode, cval, 0, 0, 0, (bf16_t*)out);
-  else
-    PYTC_REQUIRE(false, "gather_windows: bad out_dtype %d", out_dtype);
+  PYTC_DISPATCH_DTYPE(out_dtype, "gather_windows", T,
+                      hipLaunchKernelGGL(gather_windows_kernel<T>, grid, block, 0, s, vol, C, Z, Y, X, st, rz, ry, rx, view, pad_mode,
+                                         cval, 0, 0, 0, (T*)out));
   PYTC_LAUNCH_CHECK("gather_windows");
   return PYTC_OK;
 }
@@ -406,16 +401,9 @@ extern "C" int pytc_blend_accumulate(const void* pred, int pred_dtype, int B, co
                "blend_accumulate: border mask too large for the window");
   for (int b = 0; b < B; ++b) {
     int sz = starts[3 * b], sy = starts[3 * b + 1], sx = starts[3 * b + 2];
-    if (pred_dtype == PYTC_F32)
-      hipLaunchKernelGGL(blend_accumulate_kernel<float>, grid, block, 0, s,
-                         (const float*)pred + (long)b * per_win * C, sz, sy, sx, rz, ry, rx, C, view, wz, wy, wx,
-                         combine, floor_w, bz, by, bx, value, weight, Z, Y, X);
-    else if (pred_dtype == PYTC_BF16)
-      hipLaunchKernelGGL(blend_accumulate_kernel<bf16_t>, grid, block, 0, s,
-                         (const bf16_t*)pred + (long)b * per_win * C, sz, sy, sx, rz, ry, rx, C, view, wz, wy, wx,
-                         combine, floor_w, bz, by, bx, value, weight, Z, Y, X);
-    else
-      PYTC_REQUIRE(false, "blend_accumulate: bad pred_dtype %d", pred_dtype);
+    PYTC_DISPATCH_DTYPE(pred_dtype, "blend_accumulate", T,
+                        hipLaunchKernelGGL(blend_accumulate_kernel<T>, grid, block, 0, s, (const T*)pred + (long)b * per_win * C, sz, sy,
+                                           sx, rz, ry, rx, C, view, wz, wy, wx, combine, floor_w, bz, by, bx, value, weight, Z, Y, X));
   }
   PYTC_LAUNCH_CHECK("blend_accumulate");
   return PYTC_OK;
@@ -443,14 +431,9 @@ extern "C" int pytc_blend_accumulate_mapped(const void* pred, int pred_dtype, in
                "blend_accumulate_mapped: border mask too large for the window");
   for (int b = 0; b < B; ++b) {
     const int sz = starts[3 * b], sy = starts[3 * b + 1], sx = starts[3 * b + 2];
-    if (pred_dtype == PYTC_F32)
-      hipLaunchKernelGGL(blend_accumulate_mapped_kernel<float>, grid, block, 0, s, (const float*)pred + (long)b * per_win * C,
-                         sz, sy, sx, rz, ry, rx, C, view, wz, wy, wx, combine, floor_w, bz, by, bx, m, value, weight, Z, Y, X);
-    else if (pred_dtype == PYTC_BF16)
-      hipLaunchKernelGGL(blend_accumulate_mapped_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)pred + (long)b * per_win * C,
-                         sz, sy, sx, rz, ry, rx, C, view, wz, wy, wx, combine, floor_w, bz, by, bx, m, value, weight, Z, Y, X);
-    else
-      PYTC_REQUIRE(false, "blend_accumulate_mapped: bad pred_dtype %d", pred_dtype);
+    PYTC_DISPATCH_DTYPE(pred_dtype, "blend_accumulate_mapped", T,
+                        hipLaunchKernelGGL(blend_accumulate_mapped_kernel<T>, grid, block, 0, s, (const T*)pred + (long)b * per_win * C, sz,
+                                           sy, sx, rz, ry, rx, C, view, wz, wy, wx, combine, floor_w, bz, by, bx, m, value, weight, Z, Y, X));
   }
   PYTC_LAUNCH_CHECK("blend_accumulate_mapped");
   return PYTC_OK;
