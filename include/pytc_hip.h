@@ -315,7 +315,7 @@ typedef struct {
   int64_t rows_per_sample; /* OUTPUT rows per sample */
   int C_in, C_out;
   int in_dtype, out_dtype, w_dtype;
-  int act;              /* PYTC_ACT_* applied before the residual */
+  int act;              /* PYTC_ACT_NONE / SIGMOID / TANH / GELU applied before the residual; any other code is an error */
   int res_mode;         /* PYTC_RES_* */
   int gather;           /* 0 or 2 */
   int Di, Hi, Wi;       /* input grid (gather == 2) or output grid (RES_UPSAMPLE) */

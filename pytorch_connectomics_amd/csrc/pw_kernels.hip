@@ -261,6 +261,9 @@ extern "C" int pytc_pw_conv_fwd(const pytc_pw_args* a, void* stream) {
   p.MTt = (a->C_out + 15) / 16;
   p.act = a->act; p.gather = a->gather; p.pre_act = a->pre_act;
   PYTC_REQUIRE(a->pre_act == PYTC_ACT_NONE || a->pre_act == PYTC_ACT_GELU, "pw_conv: bad pre_act");
+  // apply_act (pw_common.h) evaluates these four; any other code used to pass through as the identity
+  PYTC_REQUIRE(a->act == PYTC_ACT_NONE || a->act == PYTC_ACT_SIGMOID || a->act == PYTC_ACT_TANH || a->act == PYTC_ACT_GELU,
+               "pw_conv: act %d is not one of PYTC_ACT_NONE / SIGMOID / TANH / GELU", a->act);
   p.rps_out = a->rows_per_sample; p.rps_in = a->rows_per_sample;
   p.Di = a->Di; p.Hi = a->Hi; p.Wi = a->Wi; p.Do = p.Ho = p.Wo = 0;
   if (a->gather == 2) {
