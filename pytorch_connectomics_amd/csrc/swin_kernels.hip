@@ -177,6 +177,9 @@ __global__ void __launch_bounds__(256) layernorm_any_bwd_kernel(const T* __restr
 }
 
 constexpr int LNA_ROWS_PER_SLOT = 256;
+// the parameter kernel's slots are gridDim.y; 65535 is a conservative constant (the smallest y limit HIP devices report), not read
+// from the device
+constexpr int LNA_MAX_SLOTS = 65535;
 
 // partial[slot][0][c] = sum dy xhat, partial[slot][1][c] = sum dy over the slot's rows (ascending); grid (ceil(C / 256), slots)
 template <typename T>
@@ -276,6 +279,11 @@ extern "C" int pytc_layernorm_any_bwd(const void* dy, const void* x, const float
                                       float* dgamma, float* dbeta, int64_t rows, int C, float eps, int dtype, void* stream) {
   if (int s = ln_any_check("layernorm_any_bwd", rows, C, dtype)) return s;
   PYTC_REQUIRE(dy && x && dx && (!dgamma || (gamma && dbeta && stats && partial)), "layernorm_any_bwd: null pointer");
+  // layernorm_any_param_kernel has its row slots on gridDim.y: past the device's limit the launch would be rejected without a name
+  const long param_slots = ((long)rows + LNA_ROWS_PER_SLOT - 1) / LNA_ROWS_PER_SLOT;          // in long: ceil_div narrows to int
+  PYTC_REQUIRE(!dgamma || param_slots <= LNA_MAX_SLOTS,
+               "layernorm_any_bwd: %ld rows are %ld parameter slots of %d rows, over the %d slots one launch takes: split the rows",
+               (long)rows, param_slots, LNA_ROWS_PER_SLOT, LNA_MAX_SLOTS);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(rows, 4));
   float2* s2 = dgamma ? reinterpret_cast<float2*>(stats) : nullptr;

@@ -688,6 +688,15 @@ __global__ void win_attn_table_grad_kernel(const float* __restrict__ partial, fl
 using namespace pytc;
 
 // ------------------------------------------------------------------------------------------------------------ C ABI
+// linear_launch puts the M tiles on gridDim.y: past the device's limit the launch itself would be rejected without a name
+constexpr int LG_MAX_M_TILES = 65535;      // conservative: the smallest y limit HIP devices report, not read from the device
+static int linear_m_tiles_check(const char* what, int M) {
+  const long tiles = ((long)M + LG_BM - 1) / LG_BM;
+  PYTC_REQUIRE(tiles <= LG_MAX_M_TILES, "%s: %d rows are %ld row tiles of %d, over the %d tiles one launch takes: split the rows",
+               what, M, tiles, LG_BM, LG_MAX_M_TILES);
+  return PYTC_OK;
+}
+
 template <typename TA, typename TB, typename TC, bool A_T, bool B_T>
 static void linear_launch(const LinParams& p, hipStream_t st) {
   dim3 grid(ceil_div(p.N, LG_BN), ceil_div(p.M, LG_BM));
@@ -700,6 +709,7 @@ extern "C" int pytc_linear_fwd(const void* x, const float* w, const float* bias,
   PYTC_REQUIRE(!pos || (pos_rows >= 1 && M % pos_rows == 0), "linear_fwd: %d rows are not a whole number of %d-row position blocks",
                M, pos_rows);
   PYTC_CHECK_DTYPE(dtype, "linear_fwd");
+  if (int s = linear_m_tiles_check("linear_fwd", M)) return s;
   LinParams p;
   memset(&p, 0, sizeof(p));
   p.A = x; p.B = w; p.C = y; p.bias = bias; p.pos = pos; p.P = pos ? pos_rows : 1; p.res = res; p.gelu_a = x_gelu;
@@ -714,6 +724,7 @@ extern "C" int pytc_linear_bwd_data(const void* dy, const float* w, const void* 
                                     void* stream) {
   PYTC_REQUIRE(dy && w && dx && M >= 1 && N >= 1 && K >= 1, "linear_bwd_data: bad arguments");
   PYTC_CHECK_DTYPE(dtype, "linear_bwd_data");
+  if (int s = linear_m_tiles_check("linear_bwd_data", M)) return s;
   LinParams p;
   memset(&p, 0, sizeof(p));
   // dx[M][K] = dy[M][N] . w[N][K]: the GEMM's (M, N, K) are (M, K, N)
@@ -730,6 +741,7 @@ extern "C" int pytc_linear_wgrad(const void* dy, const void* x, float* dw, float
   PYTC_REQUIRE(dy && x && M >= 1 && N >= 1 && K >= 1, "linear_wgrad: bad arguments");
   PYTC_REQUIRE(!dpos || (pos_rows >= 1 && M % pos_rows == 0), "linear_wgrad: bad position-block rows %d", pos_rows);
   PYTC_CHECK_DTYPE(dtype, "linear_wgrad");
+  if (int s = linear_m_tiles_check("linear_wgrad", N)) return s;      // the weight-gradient GEMM's M is the output features
   hipStream_t st = (hipStream_t)stream;
   if (dw) {
     // dw[N][K] = sum_m dy[m][n] x[m][k]: A(n, m) = dy[m][n] (transposed), B(m, k) = x[m][k]; one thread owns each output, K = M

@@ -47,6 +47,9 @@ struct UpcatParams {
 };
 
 constexpr int UP_BP = 64, UP_BQ = 64;
+// the forward and data-gradient launches put the row tiles on gridDim.y.  65535 is a conservative constant, the smallest y limit HIP
+// devices report (maxGridSize[1]); it is not read from the device, so a device that would take more is refused as well
+constexpr int UP_MAX_ROW_TILES = 65535;
 
 // child voxel of low voxel r for parity (0, 0, 0), and the replicated-face flags (bit 0: z, 1: y, 2: x) of its last planes
 __device__ __forceinline__ void upcat_row_info(const UpcatParams& p, int r, int& vbase, int& flags) {
@@ -277,6 +280,16 @@ static int upcat_check(const char* what, int N, int d, int h, int w, int D, int 
   return PYTC_OK;
 }
 
+// the row tiles of the FWD / DGRAD launches are gridDim.y: past the device's limit the launch itself would be rejected without a name
+static int upcat_row_tiles_check(const char* what, int N, int d, int h, int w) {
+  const long rows = (long)N * d * h * w;
+  const long tiles = (rows + UP_BQ - 1) / UP_BQ;          // in long: ceil_div narrows to int
+  PYTC_REQUIRE(tiles <= UP_MAX_ROW_TILES,
+               "%s: %ld low-resolution rows are %ld row tiles of %d, over the %d tiles one launch takes: split the batch", what, rows,
+               tiles, UP_BQ, UP_MAX_ROW_TILES);
+  return PYTC_OK;
+}
+
 static UpcatParams upcat_params(int N, int d, int h, int w, int D, int H, int W, int C_in, int C_e, int C_u) {
   UpcatParams p;
   memset(&p, 0, sizeof(p));
@@ -297,6 +310,7 @@ static void upcat_copy(const void* src, void* dst, long voxels, int C, int ss, i
 extern "C" int pytc_upcat_deconv2_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* cat, int N, int d,
                                       int h, int wd, int D, int H, int W, int C_in, int C_e, int C_u, int dtype, void* stream) {
   if (int st = upcat_check("upcat_deconv2_fwd", N, d, h, wd, D, H, W, C_in, C_e, C_u, dtype)) return st;
+  if (int st = upcat_row_tiles_check("upcat_deconv2_fwd", N, d, h, wd)) return st;
   PYTC_REQUIRE(x_low && w && x_e && cat, "upcat_deconv2_fwd: null pointer");
   UpcatParams p = upcat_params(N, d, h, wd, D, H, W, C_in, C_e, C_u);
   p.x_low = x_low; p.w = w; p.bias = bias; p.out = cat;
@@ -313,6 +327,7 @@ extern "C" int pytc_upcat_deconv2_fwd(const void* x_low, const float* w, const f
 extern "C" int pytc_upcat_deconv2_bwd_data(const void* dcat, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd,
                                            int D, int H, int W, int C_in, int C_e, int C_u, int dtype, void* stream) {
   if (int st = upcat_check("upcat_deconv2_bwd_data", N, d, h, wd, D, H, W, C_in, C_e, C_u, dtype)) return st;
+  if (int st = upcat_row_tiles_check("upcat_deconv2_bwd_data", N, d, h, wd)) return st;
   PYTC_REQUIRE(dcat && w, "upcat_deconv2_bwd_data: null pointer");
   UpcatParams p = upcat_params(N, d, h, wd, D, H, W, C_in, C_e, C_u);
   p.w = w; p.dcat = dcat; p.out = dx_low;
@@ -378,6 +393,7 @@ static UpcatParams upfirst_params(int N, int d, int h, int w, int C_in, int C_e,
 extern "C" int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const float* bias, const void* x_e, void* out, int N, int d,
                                         int h, int wd, int C_in, int C_e, int C_u, int dtype, void* stream) {
   if (int st = upfirst_check("deconv2_upfirst_fwd", N, d, h, wd, C_in, C_e, C_u, dtype)) return st;
+  if (int st = upcat_row_tiles_check("deconv2_upfirst_fwd", N, d, h, wd)) return st;
   PYTC_REQUIRE(x_low && w && out && (C_e == 0 || x_e), "deconv2_upfirst_fwd: null pointer");
   UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
   p.x_low = x_low; p.w = w; p.bias = bias; p.out = out;
@@ -394,6 +410,7 @@ extern "C" int pytc_deconv2_upfirst_fwd(const void* x_low, const float* w, const
 extern "C" int pytc_deconv2_upfirst_bwd_data(const void* dout, const float* w, void* dx_e, void* dx_low, int N, int d, int h, int wd,
                                              int C_in, int C_e, int C_u, int dtype, void* stream) {
   if (int st = upfirst_check("deconv2_upfirst_bwd_data", N, d, h, wd, C_in, C_e, C_u, dtype)) return st;
+  if (int st = upcat_row_tiles_check("deconv2_upfirst_bwd_data", N, d, h, wd)) return st;
   PYTC_REQUIRE(dout && w, "deconv2_upfirst_bwd_data: null pointer");
   UpcatParams p = upfirst_params(N, d, h, wd, C_in, C_e, C_u);
   p.w = w; p.dcat = dout; p.out = dx_low;

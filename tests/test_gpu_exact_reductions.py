@@ -139,12 +139,16 @@ def test_pw_wgrad_exact_at_training_sizes(c):
 PWD_CASES = [X.PwCase("L0_project_64x32", 4, 112 ** 3, 64, 32, gelu=True),
              X.PwCase("L0_up_project_128x32", 4, 112 ** 3, 128, 32, gelu=True),
              X.PwCase("L0_project_32x32", 4, 112 ** 3, 32, 32, gelu=True),
-             X.PwCase("odd_N5_16x80x48_project_64x32", 5, 16 * 80 * 48, 64, 32, gelu=True)]
+             X.PwCase("odd_N5_16x80x48_project_64x32", 5, 16 * 80 * 48, 64, 32, gelu=True),
+             X.PwCase("odd_N3_33x47x61_project_64x32", 3, 33 * 47 * 61, 64, 32, gelu=True)]      # 94 611 rows per sample: rows % 32 = 19
 
 
 @pytest.mark.parametrize("c", PWD_CASES, ids=_pw_id)
 def test_pw_wgrad_dgrad_weight_part_exact(c):
-    """The fused weight + data gradient of a mixer's projecting conv: its dW / db are the pw_wgrad(x_act=GELU) sums, exactly."""
+    """The fused weight + data gradient of a mixer's projecting conv: its dW / db are the pw_wgrad(x_act=GELU) sums, exactly, and its
+    data gradient is dhp = (dy . W) * gelu'(hp), exactly: dy and W are ternary, so a row of dy . W is an integer of magnitude <= C_out = 32,
+    and hp in {0, 16} makes gelu' exactly 1/2 and 1 (test_mixer_bwd_rc_exact) -- every dhp is a multiple of 1/2 below 2^6,
+    a bf16 number."""
     nat, ops = _ops()
     if not ops.pw_wgrad_dgrad_supported(c.c_in, c.c_out, torch.bfloat16):
         pytest.fail(f"pw_wgrad_dgrad does not cover {c.c_in} -> {c.c_out}")
@@ -156,14 +160,21 @@ def test_pw_wgrad_dgrad_weight_part_exact(c):
     w = X.ternary((c.c_out, c.c_in), 0.5, 11, dtype=torch.float32, device=DEV)
     wtp = ops.packed_paired(w, transposed=True)
     dr = ops.DeferredReduce()
-    dW, db, _dhp = ops.pw_wgrad_dgrad(hp, dy, wtp, N=c.N, rows_per_sample=c.rows, c_in=c.c_in, c_out=c.c_out, defer=dr)
+    dW, db, dhp = ops.pw_wgrad_dgrad(hp, dy, wtp, N=c.N, rows_per_sample=c.rows, c_in=c.c_in, c_out=c.c_out, defer=dr)
     used = dr.items[0][3]
     dr.flush()
     assert used == c.slots > 1
     _same(dW, want, "dW")
     _same(db, dyd.sum(0), "db")
-    dW2, db2, _ = ops.pw_wgrad_dgrad(hp, dy, wtp, N=c.N, rows_per_sample=c.rows, c_in=c.c_in, c_out=c.c_out)
-    assert torch.equal(dW2, dW) and torch.equal(db2, db)
+    assert tuple(dhp.shape) == (c.N, c.rows, c.c_in) and dhp.dtype == torch.bfloat16
+    for n in range(c.N):                                    # a sample at a time: integer sums of <= 32 ternary products, exact in fp32
+        want_dhp = (dy[n].float() @ w) * torch.where(hp[n] == 16.0, 1.0, 0.5)
+        assert float(want_dhp.abs().max()) <= c.c_out
+        bad = int((dhp[n].float() != want_dhp).sum())
+        assert bad == 0, f"dhp: {bad} of {want_dhp.numel()} elements of sample {n} differ from (dy . W) gelu'(hp)"
+    del want_dhp
+    dW2, db2, dhp2 = ops.pw_wgrad_dgrad(hp, dy, wtp, N=c.N, rows_per_sample=c.rows, c_in=c.c_in, c_out=c.c_out)
+    assert torch.equal(dW2, dW) and torch.equal(db2, db) and torch.equal(dhp2, dhp)
     with _Knobs(wgrad_dgrad_fused=0):                       # the unfused form the caller then takes: pw_wgrad(x_act=GELU)
         assert not ops.pw_wgrad_dgrad_supported(c.c_in, c.c_out, torch.bfloat16)
         dWu, dbu = ops.pw_wgrad(hp, dy, N=c.N, rows_per_sample=c.rows, c_in=c.c_in, c_out=c.c_out, x_act=nat.ACT_GELU)
