@@ -35,8 +35,10 @@ extern "C" {
  * 11: pytc_confusion_* (logits and labels counted into a K x K table of int64: the jaccard / dice / accuracy evaluation metrics).
  * 12: pytc_seg_erode_instance and pytc_label_targets (training targets from int32 instance labels: border erosion, affinities, binary,
  * boundary and polarity channels with their valid mask, in one launch).
+ * 13: pytc_augment_permute and pytc_augment_defects (device training augmentations: a signed axis permutation per sample of 4-byte
+ * elements, and the image defect chain -- fills, slab shifts, section copies, multiply-add -- walked per output voxel).
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 12
+#define PYTC_ABI_VERSION 13
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1122,6 +1124,46 @@ int pytc_seg_erode_instance(const int32_t* seg, int32_t* out, int N, int D, int 
 int pytc_label_targets_tile(void);
 int pytc_label_targets(const int32_t* const* sources, int n_sources, const pytc_label_channel* channels, int n_channels, float* values,
                        void* mask, int mask_dtype, int N, int D, int H, int W, void* stream);
+
+/* Device training augmentations (data/augmentation/build.py:741-1000, transforms.py, augment_ops.py): everything is an index map or
+ * one multiply-add, so results are exact.  Tensors are (N, C, D, H, W), contiguous; N C <= 65535, D H W < 2^30.  The tables are device
+ * arrays (one upload per batch, the caller's); every launch also takes the HOST copy the caller uploaded them from: the argument
+ * checks and the choice of kernels read that copy, never device memory, and nothing synchronises with the host.  The device copy
+ * must hold the same values (a kernel that decodes anything else from it writes nothing for that sample).
+ * pytc_augment_permute: out[n, c, o0, o1, o2] = in[n, c, i0, i1, i2], a signed axis permutation per sample, of 4-byte elements
+ *   copied as bits (int32 ids, fp32 images and masks alike).  perm: 3 N int32; entry v of output axis a of sample n names the input
+ *   axis s = v >= 0 ? v : -1 - v that output axis a runs along, backwards when v < 0: i_s = v >= 0 ? o_a : dim_a - 1 - o_a.
+ *   (0, 1, 2) is the identity: that sample is copied.  The three s must be a permutation of 0, 1, 2 (PYTC_ERR_INVALID) and an axis may
+ *   only move onto an axis of its own length, so the shape is kept (PYTC_ERR_UNSUPPORTED).  Samples that keep x on x move whole
+ *   lines; samples that move x go through padded 64 x 64 LDS tiles, so both the reads and the writes run along contiguous lines.
+ *   out must not overlap in.
+ * pytc_augment_defects: out = the fp32 image after sample n's op rows offsets[n] .. offsets[n + 1] (N + 1 int32, ascending from 0) of
+ *   `ops`, applied in order to every channel; a sample without rows is copied.  One launch: every output voxel walks its sample's rows
+ *   backwards carrying a source coordinate (z, y, x), stops at a constant or reads the input there, and then applies the
+ *   multiply-adds that follow in forward order.  A row is PYTC_AUG_ROW int32: kind, group, p[0 .. 7] (floats as their bits):
+ *   PYTC_AUG_FILL          the box [p0, p1) x [p2, p3) x [p4, p5) (z, y, x; inside the volume) becomes the constant p6.
+ *   PYTC_AUG_MOVE          slab p1 <= c < p2 along axis p0 is shifted by (p3, p4) along its two other axes in ascending order
+ *                          (axis 0: y, x; 1: z, x; 2: z, y): out[u, v] = in[u - p3, v - p4], p5 = 1 wraps (numpy.roll), p5 = 0
+ *                          fills with 0 what comes from outside.  |shift| < 2^30.
+ *   PYTC_AUG_COPY_SECTION  section z = p0 (1 <= p0 <= D - 2) becomes section p0 + p1 for p1 = -1 / +1, or for p1 = 0 the mean
+ *                          0.5f * (in[p0 - 1] + in[p0 + 1]) in fp32.  Rows that share a non-zero `group` (they must be adjacent)
+ *                          read the input of the group's first row: neighbouring lost sections do not cascade.  The rows of at most
+ *                          one group per sample may hold a mean (PYTC_ERR_UNSUPPORTED otherwise).
+ *   PYTC_AUG_MULADD        x = fl(fl(x * p0) + p1): product rounded, then the sum, no fused multiply-add (numpy's float32 result).
+ *   At most PYTC_AUG_MAX_OPS rows per sample (PYTC_ERR_UNSUPPORTED); an unknown kind or a row outside its bounds is PYTC_ERR_INVALID.
+ *   out must not overlap in.
+ * pytc_augment_tile: the voxels one workgroup covers in the line and defect kernels (a pure host query). */
+#define PYTC_AUG_ROW 10
+#define PYTC_AUG_MAX_OPS 512
+#define PYTC_AUG_FILL 0
+#define PYTC_AUG_MOVE 1
+#define PYTC_AUG_COPY_SECTION 2
+#define PYTC_AUG_MULADD 3
+int pytc_augment_tile(void);
+int pytc_augment_permute(const void* in, void* out, const int32_t* perm, const int32_t* perm_host, int N, int C, int D, int H, int W,
+                         void* stream);
+int pytc_augment_defects(const float* in, float* out, const int32_t* ops, const int32_t* offsets, const int32_t* ops_host,
+                         const int32_t* offsets_host, int N, int C, int D, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

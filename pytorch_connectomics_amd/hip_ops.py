@@ -2777,3 +2777,74 @@ def label_targets(sources: Sequence[torch.Tensor], channels, *, mask: bool = Tru
          nat.lib().pytc_label_targets, ptrs, len(sources), channels, C_, _p(values), _p(m),
          nat.LABEL_MASK_F32 if mask_dtype == torch.float32 else nat.LABEL_MASK_U8, N, D, H, W, _stream(), symbol="label_targets")
     return values, m
+
+
+# ------------------------------------------------------------------ training augmentations
+def _host_i32(a, name: str, shape):
+    """A host table as the C-contiguous int32 numpy array the launch checks (the copy the device table was uploaded from)."""
+    import numpy as np
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or not a.flags.c_contiguous or tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a C-contiguous int32 numpy array of shape {tuple(shape)}, got "
+                         f"{getattr(a, 'dtype', type(a).__name__)} {getattr(a, 'shape', '')}")
+    return C.c_void_p(a.ctypes.data)
+
+
+def _device_i32(t, name: str, numel: int) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name} must be a contiguous int32 CUDA(HIP) tensor of {numel} elements")
+
+
+def _augment_operand(t, name: str, dtypes) -> torch.Tensor:
+    _on_device(t, name)
+    if t.dtype not in dtypes or t.dim() != 5 or t.numel() == 0 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a non-empty contiguous (N, C, D, H, W) tensor of {' / '.join(str(d) for d in dtypes)}, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def augment_permute(x: torch.Tensor, perm: torch.Tensor, perm_host, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A signed axis permutation per sample of a 4-byte (N, C, D, H, W) tensor, int32 ids or fp32, copied as bits
+    (include/pytc_hip.h pytc_augment_permute).  perm: int32 device tensor of 3 N entries; perm_host: the (N, 3) int32 numpy array it was
+    uploaded from (the checks and the kernel choice read this copy).  A batch whose permutations are all the identity launches
+    nothing and returns `x` itself.  `out` must not alias `x`."""
+    _augment_operand(x, "x", (torch.int32, torch.float32))
+    N, C_, D, H, W = (int(v) for v in x.shape)
+    host = _host_i32(perm_host, "perm_host", (N, 3))
+    _device_i32(perm, "perm", 3 * N)
+    if out is None and bool((perm_host == (0, 1, 2)).all()):
+        return x
+    if out is None:
+        out = torch.empty_like(x)
+    _augment_operand(out, "out", (x.dtype,))
+    if out.shape != x.shape:
+        raise ValueError(f"out must have the input's shape {tuple(x.shape)}, got {tuple(out.shape)}")
+    _run("augment_permute", _nbytes(x, out), nat.lib().pytc_augment_permute, _p(x), _p(out), _p(perm), host, N, C_, D, H, W, _stream(),
+         symbol="aug_permute")
+    return out
+
+
+def augment_defects(image: torch.Tensor, ops: Optional[torch.Tensor], offsets: torch.Tensor, ops_host, offsets_host,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The image defect chain of a batch in one launch (include/pytc_hip.h pytc_augment_defects).  image: fp32 (N, C, D, H, W);
+    ops: int32 device tensor of rows x PYTC_AUG_ROW entries (None without rows); offsets: int32 device tensor of N + 1 row offsets;
+    ops_host (rows, PYTC_AUG_ROW) / offsets_host (N + 1,): the int32 numpy arrays they were uploaded from.  A batch without rows
+    launches nothing and returns `image` itself.  `out` must not alias `image`."""
+    _augment_operand(image, "image", (torch.float32,))
+    N, C_, D, H, W = (int(v) for v in image.shape)
+    off_host = _host_i32(offsets_host, "offsets_host", (N + 1,))
+    rows = int(offsets_host[N])
+    _device_i32(offsets, "offsets", N + 1)
+    ops_h = None
+    if rows > 0:
+        ops_h = _host_i32(ops_host, "ops_host", (rows, nat.AUG_ROW))
+        _device_i32(ops, "ops", rows * nat.AUG_ROW)
+    elif out is None and rows == 0:
+        return image
+    if out is None:
+        out = torch.empty_like(image)
+    _augment_operand(out, "out", (torch.float32,))
+    if out.shape != image.shape:
+        raise ValueError(f"out must have the image's shape {tuple(image.shape)}, got {tuple(out.shape)}")
+    _run(f"augment_defects[{rows}]", _nbytes(image, out), nat.lib().pytc_augment_defects, _p(image), _p(out), _p(ops) if rows > 0 else None,
+         _p(offsets), ops_h, off_host, N, C_, D, H, W, _stream(), symbol="aug_defects")
+    return out

@@ -282,14 +282,23 @@ def train_batches(cfg, module, dev, *, rank: int = 0, demo: bool = False):
     """The endless batch iterator of `run_train`: synthetic (random://) batches, or patches sampled from .npy volumes.  With a real
     label volume and non-empty `data.label_transform.targets` the label stays an integer volume (range-checked to int32, never a
     float), the sampler yields id patches and the device transform (data/label_targets.py) turns each batch into the stacked targets
-    and their `label_mask`; every other configuration feeds `label > 0` or the class numbers as before."""
+    and their `label_mask`; every other configuration feeds `label > 0` or the class numbers as before.  Enabled `data.augmentation`
+    blocks act on the device between the two: flips, quarter turns and axis permutations on image and label, section defects on the image
+    (data/augment.py)."""
     from .training import synthetic_batches
     patch = tuple(cfg.data.dataloader.patch_size or cfg.model.input_size or (64, 64, 64))
     bs = int(cfg.data.dataloader.batch_size)
     img_spec = cfg.data.train.image
     if img_spec is None or str(img_spec).startswith("random://") or demo:
+        # synthetic batches run as they always did: data.augmentation is neither planned nor refused for them
         return synthetic_batches(bs, patch, in_channels=cfg.model.in_channels, out_channels=cfg.model.out_channels,
                                  seed=int(cfg.system.seed) + rank, device=dev)
+    # data.augmentation: planned before the volume is read, so that a refused block fails here (data/augment.py); its random states are
+    # its own, the sampler's generator below draws the same patch offsets with and without it
+    from .data import AugmentationPlan, augmented_batches
+    augment = AugmentationPlan.from_config(getattr(cfg.data, "augmentation", None), seed=int(cfg.system.seed) + rank,
+                                           in_channels=int(cfg.model.in_channels), patch_size=patch if len(patch) == 3 else None,
+                                           do_2d=len(patch) != 3 or bool(getattr(cfg.data.train, "do_2d", False)))
     from .utils.volume_normalize import normalize_image_for_config
     vol = torch.from_numpy(np.ascontiguousarray(normalize_image_for_config(read_volume(str(img_spec)), cfg), dtype=np.float32))
     g = torch.Generator().manual_seed(int(cfg.system.seed) + rank)
@@ -327,9 +336,12 @@ def train_batches(cfg, module, dev, *, rank: int = 0, demo: bool = False):
                 else:
                     ys.append((yv if keep_classes else (yv > 0).float())[None])
             yield {"image": torch.stack(xs), "label": torch.stack(ys)}
+    # the reference's seam (data/augmentation/build.py:309-334): after the crop and the normalisation, before the label erosion and the
+    # targets.  A plan with nothing to do wraps nothing: the same batches, no launch, no draw
+    source = augmented_batches(sampler(), augment, dev) if augment.enabled else sampler()
     if plan is None:
-        return sampler()
-    batches = device_target_batches(sampler(), plan, dev, mask_dtype=torch.float32)
+        return source
+    batches = device_target_batches(source, plan, dev, mask_dtype=torch.float32)
     if len(patch) == 3:
         return batches
     return ({k: (v.squeeze(2) if k in ("label", "label_mask") else v) for k, v in b.items()} for b in batches)
