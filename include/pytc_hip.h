@@ -37,8 +37,10 @@ extern "C" {
  * boundary and polarity channels with their valid mask, in one launch).
  * 13: pytc_augment_permute and pytc_augment_defects (device training augmentations: a signed axis permutation per sample of 4-byte
  * elements, and the image defect chain -- fills, slab shifts, section copies, multiply-add -- walked per output voxel).
+ * 14: pytc_affinity_cc (connected components of a thresholded affinity graph: union-find, ids in raster order) and PYTC_F16, the
+ * dtype code only that entry takes.
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 13
+#define PYTC_ABI_VERSION 14
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -47,6 +49,7 @@ extern "C" {
 
 #define PYTC_F32 0
 #define PYTC_BF16 1
+#define PYTC_F16 2 /* stored predictions only: pytc_affinity_cc reads it; every other entry refuses it as a bad dtype */
 
 /* window "view" bits (test-time-augmentation as index math, inference/tta.py:712-719,1026-1060) */
 #define PYTC_VIEW_FLIP_Z 1
@@ -1164,6 +1167,25 @@ int pytc_augment_permute(const void* in, void* out, const int32_t* perm, const i
                          void* stream);
 int pytc_augment_defects(const float* in, float* out, const int32_t* ops, const int32_t* offsets, const int32_t* ops_host,
                          const int32_t* offsets_host, int N, int C, int D, int H, int W, void* stream);
+
+/* Connected components of a thresholded affinity graph (decoding/decoders/segmentation.py:498-655 decode_affinity_cc with its numba /
+ * numba_serial / cupy backends, segmentation_kernels.py:109-210): integers only, the ids are the reference's bit for bit.
+ *   c0, c1, c2   the affinity channel of axis 0, 1, 2: three device pointers to contiguous (A0, A1, A2) blocks of `dtype` (PYTC_F32,
+ *                PYTC_BF16 or PYTC_F16), anywhere in memory -- the channels of one tensor at any channel stride and in any order
+ *   threshold    hard[a][v] = channel a at v > threshold, strict, NaN false; the caller rounds the threshold to `dtype` first
+ *   edge_offset  0 or 1: voxels v and v + unit_a are joined iff v + unit_a lies inside the volume and hard[a][v + edge_offset unit_a]
+ *   edges        A0 A1 A2 bytes of scratch      parent  A0 A1 A2 uint32 of scratch      counts  pytc_affinity_cc_blocks(A0 A1 A2) int32
+ *   labels       int32 (A0, A1, A2): 0 = background (no hard channel at v and no edge ends there), else 1 .. K in raster order of every
+ *                component's smallest voxel with a hard channel (where the reference's flood fill starts)      count  one int32: K
+ * A0 A1 A2 < 2^31 - 1.  No buffer may overlap another or a channel.  Eight launches on `stream`, nine with edge_offset 1
+ * (csrc/cc_kernels.hip): union-find in LDS per 8 x 8 x 32 tile, agent-scope atomicMin across tile faces, a prefix count of the
+ * components' first voxels by per-block counts and one scanning workgroup.  No launch waits for another workgroup, nothing is read
+ * back, nothing synchronises with the host.
+ * pytc_affinity_cc_tile(axis): the tile extent along axis 0 / 1 / 2 (host queries; tests size their edge cases with them). */
+int pytc_affinity_cc_tile(int axis);
+int64_t pytc_affinity_cc_blocks(int64_t voxels);
+int pytc_affinity_cc(const void* c0, const void* c1, const void* c2, int dtype, float threshold, int edge_offset, void* edges, void* parent,
+                     int32_t* counts, int32_t* labels, int32_t* count, int A0, int A1, int A2, void* stream);
 
 #ifdef __cplusplus
 }

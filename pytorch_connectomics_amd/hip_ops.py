@@ -2848,3 +2848,46 @@ def augment_defects(image: torch.Tensor, ops: Optional[torch.Tensor], offsets: t
     _run(f"augment_defects[{rows}]", _nbytes(image, out), nat.lib().pytc_augment_defects, _p(image), _p(out), _p(ops) if rows > 0 else None,
          _p(offsets), ops_h, off_host, N, C_, D, H, W, _stream(), symbol="aug_defects")
     return out
+
+
+# ------------------------------------------------------------------ affinity connected components (csrc/cc_kernels.hip)
+_CC_DT = {torch.float32: nat.F32, torch.bfloat16: nat.BF16, torch.float16: nat.F16}
+
+
+def affinity_cc(aff: torch.Tensor, threshold: float, edge_offset: int = 0, channels: Sequence[int] = (0, 1, 2)):
+    """Connected components of the thresholded affinity graph of `aff` (C, A0, A1, A2), fp32 / fp16 / bf16 (include/pytc_hip.h
+    pytc_affinity_cc): channels[a] is the affinity of axis a; voxels v and v + unit_a are joined iff v + unit_a lies inside the volume
+    and aff[channels[a]] > threshold (strict, the threshold rounded to the tensor's dtype first) at v + edge_offset unit_a.
+    -> (labels int32 (A0, A1, A2): 0 background, 1 .. K in raster order of every component's first voxel with a channel above the
+    threshold, the order of the reference's flood fill; count int32[1] = K), both on
+    the device, on the current stream, nothing synchronised.  Any channel stride is read in place; a channel's spatial block must be
+    contiguous."""
+    _on_device(aff, "aff")
+    if aff.dim() != 4 or aff.numel() == 0 or aff.dtype not in _CC_DT:
+        raise ValueError(f"aff must be a non-empty (C, A0, A1, A2) tensor of float32 / float16 / bfloat16, got {aff.dtype} {tuple(aff.shape)}")
+    channels = [int(c) for c in channels]
+    if len(channels) != 3 or any(not 0 <= c < aff.shape[0] for c in channels):
+        raise ValueError(f"channels must name three of the {aff.shape[0]} channels, got {channels}")
+    if int(edge_offset) not in (0, 1):
+        raise ValueError(f"edge_offset must be 0 or 1, got {edge_offset}")
+    A0, A1, A2 = (int(v) for v in aff.shape[1:])
+    V = A0 * A1 * A2
+    if V >= 2 ** 31 - 1:
+        raise NotImplementedError(f"affinities of {V} voxels: ids and indices are 31 bits (a volume of 2^31 - 1 voxels or more is not built)")
+    planes = [aff[c] for c in channels]
+    if any(not p.is_contiguous() for p in planes):
+        raise ValueError(f"every channel of aff must be a contiguous (A0, A1, A2) block, got strides {tuple(aff.stride())}")
+    # numpy compares a float16 / float32 array with the Python scalar rounded to the array's dtype; bfloat16 follows the same rule
+    thr = float(torch.tensor(float(threshold), dtype=torch.float64).to(aff.dtype))
+    dev = aff.device
+    edges = torch.empty(V, dtype=torch.uint8, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    counts = torch.empty(int(nat.lib().pytc_affinity_cc_blocks(V)), dtype=torch.int32, device=dev)
+    labels = torch.empty((A0, A1, A2), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    # algorithmic bytes: the three planes once, the edge byte written and read by local and merge, parent written by local, read and
+    # written by flatten and rank, read by apply, the labels written
+    _run(f"affinity_cc[e={int(edge_offset)}]", V * (3 * aff.element_size() + 3 + 6 * 4 + 4), nat.lib().pytc_affinity_cc,
+         _p(planes[0]), _p(planes[1]), _p(planes[2]), _CC_DT[aff.dtype], thr, int(edge_offset), _p(edges), _p(parent), _p(counts),
+         _p(labels), _p(count), A0, A1, A2, _stream(), symbol="affinity_cc")
+    return labels, count

@@ -5,6 +5,7 @@
 
 test : build_model(cfg) -> load checkpoint -> volume to HBM -> InferenceManager.predict_with_tta (or chunked
        inference when inference.chunking.enabled) -> optional binary Jaccard -> <save_path>/results/*_prediction.h5 (the CZYX raw-prediction artifact)
+       -> with a `decoding.steps` entry `decode_affinity_cc`: connected components on the device -> results/*_segmentation.h5
 train: training/module.py's Lightning-free harness (HIP forward + backward, fused loss, fused clip + AdamW), one process
        per GPU under torch.distributed.run (DDP over RCCL); writes checkpoints/last.ckpt in the Lightning layout.
 Volumes: .npy / .npz (first array) / random://<name>[?shape=Z,Y,X] / .h5 (dataset `main`; h5py or the in-repo libhdf5 shim).
@@ -169,6 +170,8 @@ def run_test(cfg, args) -> dict:
     if not torch.cuda.is_available():
         raise RuntimeError("test mode needs an MI355X (ROCm) device: this engine has no CPU path")
     dev = torch.device("cuda", 0)
+    from .decoding import compact_labels, plan_decoding, run_decoding
+    decode_plan = plan_decoding(cfg)                          # a decoding step this engine does not build fails here, before the inference
     torch.manual_seed(int(cfg.system.seed))
     model = build_model(cfg).to(dev).eval()
     if args.checkpoint:
@@ -266,6 +269,19 @@ def run_test(cfg, args) -> dict:
         # channel 0 of the prediction where it lies (device: the HIP count kernel; the chunked path's host array: torch on the CPU)
         metrics.update(voxel_metrics(pred_t[0, 0], torch.from_numpy(lab), names or None,
                                      float(getattr(ev, "prediction_threshold", 0.5)) if ev is not None else 0.5))
+    if decode_plan is not None and pred_t is not None:
+        # decoding.steps: instances from the prediction where it lies (the chunked path's host array is uploaded); the ids come back
+        # once, as int32, and are stored in the reference's compact dtype
+        from .utils.h5lite import get_h5_backend
+        t1 = time.perf_counter()
+        seg = compact_labels(run_decoding(cfg, pred_t[0].to(dev)).cpu().numpy())
+        metrics["instances"] = int(seg.max()) if seg.size else 0
+        metrics["decode_seconds"] = time.perf_counter() - t1
+        be = get_h5_backend()
+        if be is None:
+            raise RuntimeError("writing the segmentation needs h5py or the in-repo libpytc_h5.so (built from csrc/host/h5io.c against libhdf5)")
+        with be.File(out_dir / f"{name}_segmentation.h5", "w") as fh:
+            fh.create_dataset("main", data=seg)
     (out_dir / f"{name}_metrics.json").write_text(json.dumps(metrics, indent=2))
     logger.info("test done: %s", metrics)
     return metrics
