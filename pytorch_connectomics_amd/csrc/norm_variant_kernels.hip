@@ -10,12 +10,7 @@
 
 namespace pytc {
 
-// d/dx [x * Phi(x)] with libm erff -- the same derivative gelu_kernel / RES_GELU_BWD apply (train_kernels.hip gelu_grad)
-__device__ __forceinline__ float gelu_grad_erf(float x) {
-  const float phi_big = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-  return phi_big + x * pdf;
-}
+// gelu_erf / gelu_grad (libm erff: the derivative gelu_kernel applies; RES_GELU_BWD applies gelu_erf_grad): pytc_common.h
 
 // L = C / VEC lanes share a row (power of two <= 64, same mapping as layernorm_rows_kernel).  Per row:
 //   xhat = (x - mean) * rstd,  g = dy * gamma,  dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))
@@ -95,7 +90,7 @@ grn_bwd_apply_kernel(const T* __restrict__ dh2, const T* __restrict__ hp, const 
     // the forward's h is gelu(hp) ROUNDED to the storage type (pytc_gelu writes T): use the same value here
     const float h = to_f32<T>(from_f32<T>(gelu_erf(p)));
     const float dh = fmaf(to_f32<T>(dh2[i]), A[n * C + c], h * B[n * C + c]);
-    out[i] = from_f32<T>(dh * gelu_grad_erf(p));
+    out[i] = from_f32<T>(dh * gelu_grad(p));
   }
 }
 

@@ -184,8 +184,11 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 }
 
 // erf GELU (torch.nn.functional.gelu(approximate='none')) with erf from Abramowitz-Stegun 7.1.26
-// (|abs err| <= 1.5e-7), evaluated as 1+erf(z) = p(t)exp(-z^2) for z<0 and 2 - p(t)exp(-z^2) for
-// z>0 so the negative tail has no cancellation.  ~14 VALU + v_rcp_f32 + v_exp_f32, branch free.
+// (|abs err| <= 1.5e-7; 1.394e-7 measured over every bf16 value), evaluated as 1+erf(z) = p(t)exp(-z^2) for z<0 and
+// 2 - p(t)exp(-z^2) for z>0, so the negative tail is not formed as a difference of nearly equal numbers.  That makes the tail
+// ABSOLUTELY accurate (|gelu_erf - gelu| <= 2.11e-7 everywhere), not relatively accurate: the A&S tail behaves as 0.778/z against
+// the true 1/(sqrt(pi) z), so the relative error for x < 0 grows to 0.44 where the value itself has underflowed to ~1e-30 and below.
+// ~14 VALU + v_rcp_f32 + v_exp_f32, branch free.  Every claim here: tests/test_host_activation_domain_cases.py.
 __device__ __forceinline__ float gelu_erf(float x) {
   const float az = fabsf(x) * 0.70710678118654752440f;
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, az, 1.0f));
@@ -194,8 +197,12 @@ __device__ __forceinline__ float gelu_erf(float x) {
   p = fmaf(t, p, -0.284496736f);
   p = fmaf(t, p, 0.254829592f);
   p *= t;
-  const float pe = p * __builtin_amdgcn_exp2f(-az * az * 1.44269504088896340736f);
-  const float one_plus_erf = x < 0.f ? pe : 2.0f - pe;
+  const float e = __builtin_amdgcn_exp2f(-az * az * 1.44269504088896340736f);
+  // 2 - p e as ONE fma, written out: left to the compiler, "2.0f - p * e" became v_fma_f32 at scalar call sites and v_pk_mul_f32 +
+  // v_sub_f32 where the SLP vectoriser packed the call site (pw_conv_kernel's pre_act prologue and RES_GELU_BWD epilogue), one fp32 ulp
+  // apart at 0.5 % of the positive inputs -- the same function must give the same bits wherever it is called
+  // (tests/test_gpu_activation_domain.py test_same_function_same_bits)
+  const float one_plus_erf = x < 0.f ? p * e : fmaf(-p, e, 2.0f);
   return 0.5f * x * one_plus_erf;
 }
 
@@ -209,13 +216,20 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   p = fmaf(t, p, 0.254829592f);
   p *= t;
   const float e = __builtin_amdgcn_exp2f(-az * az * 1.44269504088896340736f);     // exp(-x^2/2)
-  const float pe = p * e;
-  const float one_plus_erf = x < 0.f ? pe : 2.0f - pe;
+  const float one_plus_erf = x < 0.f ? p * e : fmaf(-p, e, 2.0f);                  // one fma, as in gelu_erf
   return fmaf(x * 0.3989422804014327f, e, 0.5f * one_plus_erf);
 }
 
+// d/dx [x * Phi(x)] = Phi(x) + x * phi(x) with libm erff and __expf: the derivative pytc_gelu(dy) and grn_bwd_apply multiply by
+// (RES_GELU_BWD and the linear layers' data gradient use gelu_erf_grad above; the two agree to 6.97e-8 + libm's own error)
+__device__ __forceinline__ float gelu_grad(float x) {
+  const float phi_big = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
+  const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+  return phi_big + x * pdf;
+}
+
 // Sigmoid-form GELU for the bf16 fast path:  x * sigmoid(x * (a + b x^2 + c x^4)), minimax fit of the erf
-// GELU on [-8, 8] (max abs error 2.5e-5, i.e. far below the bf16 rounding of the activation it feeds);
+// GELU on [-8, 8] (max abs error 2.52e-5, i.e. far below the bf16 rounding of the activation it feeds);
 // x^2 is clamped at 64 so the odd polynomial keeps its sign outside the fitted range (sigmoid is saturated
 // there).  7 VALU + v_exp_f32 + v_rcp_f32, about half the cost of gelu_erf.
 __device__ __forceinline__ float gelu_fast(float x) {

@@ -8,13 +8,7 @@
 
 namespace pytc {
 
-__device__ __forceinline__ float gelu_grad(float x) {
-  // d/dx [x * Phi(x)] = Phi(x) + x * phi(x)
-  const float phi_big = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-  return phi_big + x * pdf;
-}
-
+// gelu_erf / gelu_grad: pytc_common.h
 template <typename T>
 __global__ void __launch_bounds__(256)
 gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out, long n) {
