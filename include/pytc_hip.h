@@ -39,8 +39,10 @@ extern "C" {
  * elements, and the image defect chain -- fills, slab shifts, section copies, multiply-add -- walked per output voxel).
  * 14: pytc_affinity_cc (connected components of a thresholded affinity graph: union-find, ids in raster order) and PYTC_F16, the
  * dtype code only that entry takes.
+ * 15: pytc_pair_table_runs / _build / _matches (the sparse contingency table of two id volumes and the integer record adapted Rand, VOI
+ * and instance matching are functions of) with their host queries, and pytc_pair_hash.
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 14
+#define PYTC_ABI_VERSION 15
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1186,6 +1188,46 @@ int pytc_affinity_cc_tile(int axis);
 int64_t pytc_affinity_cc_blocks(int64_t voxels);
 int pytc_affinity_cc(const void* c0, const void* c1, const void* c2, int dtype, float threshold, int edge_offset, void* edges, void* parent,
                      int32_t* counts, int32_t* labels, int32_t* count, int A0, int A1, int A2, void* stream);
+
+/* The label-pair table of two id volumes (metrics/segmentation_numpy.py adapted_rand, voi, instance_matching, instance_matching_simple):
+ * n[g][s] = the voxels with ground-truth id g and segmentation id s, as an open-addressing hash table, and the integer record those
+ * metrics are functions of (csrc/pair_table_kernels.hip, csrc/pair_table_core.h).
+ *   gt, seg      two contiguous device volumes of n ids, 16-byte aligned, gt_bytes / seg_bytes = 4 (int32) or 8 (int64) in any
+ *                combination; 0 = background, every id in 0 .. 2^31 - 2; 1 <= n <= 2^31 - 2
+ * pytc_pair_table_runs: one launch.  bound[0] = U, the positions whose (gt, seg) differs from its predecessor in memory order (the
+ *   first voxel counts), an upper bound of the number of distinct pairs; bound[1] = bit 0 / bit 1 set when gt / seg holds an id outside
+ *   the range.  The caller reads both, refuses a set bit and calls _build with runs = U and cap = pytc_pair_table_capacity(U), the
+ *   smallest power of two >= 2 U and >= 256.
+ * pytc_pair_table_build: clears `table` and `record` and enqueues four launches (build, marginals, sums, finish).  PYTC_ERR_INVALID for
+ *   a cap that is no power of two, below 256 or below 2 runs: cap >= twice the number of keys is what bounds the probe loop.
+ *   table        6 cap int64 of scratch: the keys of the pair table (gt << 32 | seg), of the table of gt ids and of the table of seg
+ *                ids, cap each, an empty key all ones; then their values: the count n, A[g], and Bfull[s] << 32 | B1[s]
+ *   record       pytc_pair_table_record_cells() = 16 int64:  0 N   1 N1 = voxels with gt >= 1   2 S_A = sum_{g>=1} A[g]^2
+ *                3 S_B = sum_{s>=1} B1[s]^2   4 S_AB = sum_{g,s>=1} n^2   5 c = sum_{g>=1} n[g][0]   6 n_true   7 n_pred (distinct ids
+ *                >= 1)   8 P = distinct pairs   9 updates of the global pair table by the build (at most one per workgroup and distinct
+ *                pair of it, plus what overflowed its LDS table)   10 X_N = sum_{g>=1, s} n log2 n   11 X_A = sum_{g>=1} A log2 A
+ *                12 X_B = sum_s B1 log2 B1, each term rounded to 27 fractional bits before it is added   13 non-zero: an insert or a
+ *                lookup ran out of probes (the caller passed a `runs` below the truth)   14 X_A - X_N = N1 H(seg | gt)
+ *                15 X_B - X_N = N1 H(gt | seg), both in 27-bit fixed point.  A[g] = sum_s n, Bfull[s] = sum_g n, B1[s] = sum_{g>=1} n.
+ *                Every cell is an integer sum: exact, and the same bits from call to call.
+ * pytc_pair_table_matches: one launch over a built table.  A pair g, s >= 1 passes iff float32(float64(n) / float64(A[g] + Bfull[s] - n))
+ *   >= thresh.  count[0] = the passing pairs, count[1] non-zero on a failed lookup; pairs[2 k], pairs[2 k + 1] = (g, s) of the k-th one,
+ *   in no particular order, for k < pairs_cap (P pairs always suffice).
+ * Nothing synchronises with the host; everything runs on `stream`.  No allocation is proportional to the largest id.
+ * Host queries: the voxels a lane reads in a row, the voxels of a workgroup's pass, the slots of a workgroup's LDS table, the cells of
+ * the record, the workgroups the build launches for a volume, the capacity for a run count (-1: out of range), and
+ * pytc_pair_hash(gt, seg, log2_cap): the slot of a table of 2^log2_cap slots at which the probe of a pair starts (-1: out of range). */
+int64_t pytc_pair_table_lane_run(void);
+int64_t pytc_pair_table_span(void);
+int64_t pytc_pair_table_lds_slots(void);
+int64_t pytc_pair_table_record_cells(void);
+int64_t pytc_pair_table_workgroups(int64_t voxels);
+int64_t pytc_pair_table_capacity(int64_t runs);
+int64_t pytc_pair_hash(int64_t gt, int64_t seg, int log2_cap);
+int pytc_pair_table_runs(const void* gt, int gt_bytes, const void* seg, int seg_bytes, int64_t n, int64_t* bound, void* stream);
+int pytc_pair_table_build(const void* gt, int gt_bytes, const void* seg, int seg_bytes, int64_t n, int64_t runs, void* table, int64_t cap,
+                          int64_t* record, void* stream);
+int pytc_pair_table_matches(const void* table, int64_t cap, float thresh, int32_t* pairs, int64_t pairs_cap, int64_t* count, void* stream);
 
 #ifdef __cplusplus
 }

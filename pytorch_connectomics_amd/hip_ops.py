@@ -2891,3 +2891,88 @@ def affinity_cc(aff: torch.Tensor, threshold: float, edge_offset: int = 0, chann
          _p(planes[0]), _p(planes[1]), _p(planes[2]), _CC_DT[aff.dtype], thr, int(edge_offset), _p(edges), _p(parent), _p(counts),
          _p(labels), _p(count), A0, A1, A2, _stream(), symbol="affinity_cc")
     return labels, count
+
+
+# ------------------------------------------------------------------ label-pair table (csrc/pair_table_kernels.hip)
+PAIR_RECORD_CELLS = ("N", "N1", "S_A", "S_B", "S_AB", "c", "n_true", "n_pred", "pairs", "global_updates", "x_n", "x_a", "x_b", "lost",
+                     "voi_split_fixed", "voi_merge_fixed")
+
+
+class PairTable:
+    """The sparse contingency table of two id volumes on the device and its integer record (include/pytc_hip.h pytc_pair_table_*).
+    `record()` reads the 16 cells once; `matches(thresh)` reads the count of passing pairs and then that many pairs."""
+
+    def __init__(self, table: torch.Tensor, cap: int, cells: torch.Tensor, runs: int, workgroups: int):
+        self.table, self.cap, self.cells, self.runs, self.workgroups = table, int(cap), cells, int(runs), int(workgroups)
+        self._record = None
+
+    def record(self) -> dict:
+        """The record as a host dict of Python ints (PAIR_RECORD_CELLS), read once."""
+        if self._record is None:
+            rec = dict(zip(PAIR_RECORD_CELLS, (int(v) for v in self.cells.tolist())))
+            if rec["lost"]:
+                raise RuntimeError(f"label_pair_table: {rec['lost']} inserts or lookups ran out of probes in a table of {self.cap} slots")
+            self._record = rec
+        return self._record
+
+    def matches(self, thresh: float):
+        """-> (pairs int64 (K, 2), K): the (gt id, seg id) pairs, both >= 1, whose float32 IoU score is >= float32(thresh), sorted by
+        gt id and then seg id, and their number (the reference's instance_matching_simple `tp`)."""
+        P = max(1, self.record()["pairs"])
+        dev = self.table.device
+        pairs = torch.empty((P, 2), dtype=torch.int32, device=dev)
+        count = torch.empty(2, dtype=torch.int64, device=dev)
+        thr = float(torch.tensor(float(thresh), dtype=torch.float32))
+        _run("pair_table_matches", 48 * self.cap, nat.lib().pytc_pair_table_matches, _p(self.table), self.cap, thr, _p(pairs), P, _p(count),
+             _stream(), symbol="pt_matches")
+        k, lost = (int(v) for v in count.tolist())
+        if lost or k > P:
+            raise RuntimeError(f"label_pair_table.matches: {lost} failed lookups, {k} passing pairs of {P}")
+        got = pairs[:k].cpu().numpy().astype("int64")
+        order = (got[:, 0] * (1 << 32) + got[:, 1]).argsort(kind="stable")
+        return got[order], k
+
+
+def _id_volume(t: torch.Tensor, name: str) -> torch.Tensor:
+    _on_device(t, name)
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise ValueError(f"{name} must hold integer ids, got {t.dtype}")
+    if t.dtype not in (torch.int32, torch.int64):            # one cast: the narrow and boolean dtypes fit int32, the wide unsigned ones int64
+        t = t.to(torch.int32 if t.element_size() < 4 or t.dtype == torch.bool else torch.int64)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.data_ptr() % 16:                                    # a view that starts inside an allocation: the kernels read 16-byte vectors
+        t = t.clone()
+    return t
+
+
+def label_pair_table(seg: torch.Tensor, gt: torch.Tensor) -> PairTable:
+    """The table n[g][s] of the voxels with ground-truth id g and segmentation id s (0 = background, ids 0 .. 2^31 - 2) of two device
+    tensors of equal shape, int32 or int64 in any combination (other integer dtypes are cast once, a non-contiguous tensor is copied
+    once), on the current stream.  One host read in here: the run count U that sizes the table (the smallest power of two >= 2 U slots
+    of 48 bytes, from torch's caching allocator) and the flag of an id outside the range, which raises ValueError naming the operand."""
+    if tuple(seg.shape) != tuple(gt.shape):
+        raise ValueError(f"seg and gt must have the same shape. Got seg.shape={tuple(seg.shape)}, gt.shape={tuple(gt.shape)}")
+    seg, gt = _id_volume(seg, "seg"), _id_volume(gt, "gt")
+    n = seg.numel()
+    if n < 1:
+        raise ValueError("seg and gt are empty")
+    if n >= 2 ** 31 - 1:
+        raise NotImplementedError(f"volumes of {n} voxels: counts and ids are 31 bits (a volume of 2^31 - 1 voxels or more is not built)")
+    lib, dev = nat.lib(), seg.device
+    bound = torch.empty(2, dtype=torch.int64, device=dev)
+    _run("pair_table_runs", _nbytes(seg, gt), lib.pytc_pair_table_runs, _p(gt), gt.element_size(), _p(seg), seg.element_size(), n,
+         _p(bound), _stream(), symbol="pt_runs")
+    runs, flag = (int(v) for v in bound.tolist())
+    if flag:
+        names = [name for bit, name in ((1, "gt"), (2, "seg")) if flag & bit]
+        raise ValueError(f"{' and '.join(names)} must hold ids in 0 .. 2^31 - 2: a negative id or an id >= 2^31 - 1 was found")
+    cap = int(lib.pytc_pair_table_capacity(runs))
+    if cap < 2 * runs:
+        raise RuntimeError(f"label_pair_table: no capacity for {runs} runs")
+    table = torch.empty(6 * cap, dtype=torch.int64, device=dev)
+    cells = torch.empty(len(PAIR_RECORD_CELLS), dtype=torch.int64, device=dev)
+    # algorithmic bytes: both volumes once, the tables cleared, then read by the marginals and the sums
+    _run("pair_table_build", _nbytes(seg, gt) + 3 * 48 * cap, lib.pytc_pair_table_build, _p(gt), gt.element_size(), _p(seg),
+         seg.element_size(), n, runs, _p(table), cap, _p(cells), _stream(), symbol="pt_build")
+    return PairTable(table, cap, cells, runs, int(lib.pytc_pair_table_workgroups(n)))

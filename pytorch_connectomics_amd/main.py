@@ -6,6 +6,8 @@
 test : build_model(cfg) -> load checkpoint -> volume to HBM -> InferenceManager.predict_with_tta (or chunked
        inference when inference.chunking.enabled) -> optional binary Jaccard -> <save_path>/results/*_prediction.h5 (the CZYX raw-prediction artifact)
        -> with a `decoding.steps` entry `decode_affinity_cc`: connected components on the device -> results/*_segmentation.h5
+       -> with that, a label and `evaluation.metrics` naming adapted_rand / voi / instance_accuracy[_detail]: the instance metrics from
+          one label-pair table built on the device (metrics/)
 train: training/module.py's Lightning-free harness (HIP forward + backward, fused loss, fused clip + AdamW), one process
        per GPU under torch.distributed.run (DDP over RCCL); writes checkpoints/last.ckpt in the Lightning layout.
 Volumes: .npy / .npz (first array) / random://<name>[?shape=Z,Y,X] / .h5 (dataset `main`; h5py or the in-repo libhdf5 shim).
@@ -257,15 +259,19 @@ def run_test(cfg, args) -> dict:
     out_vox = float(np.prod(vol.shape[-3:])) if vol is not None else (float(np.prod(pred_t.shape[-3:])) if pred_t is not None else 0.0)
     metrics = {"seconds": dt, "output_voxels_per_s": out_vox / dt}
     label_spec = cfg.data.test.label
+    instance_names = []
     if label_spec and pred_t is not None:
         lab = np.array(read_volume(str(label_spec)), copy=True)                         # an own, writable array (memmaps are read-only)
         if lab.dtype not in (np.uint8, np.int64, np.float32):                           # one cast to a dtype the count kernel reads
             lab = lab.astype(np.float32 if lab.dtype.kind == "f" else np.int64)
         ev = getattr(cfg, "evaluation", None)
         names = list(getattr(ev, "metrics", None) or []) if ev is not None and bool(getattr(ev, "enabled", False)) else []
-        if any(n in INSTANCE_METRICS for n in names):
-            logger.warning("evaluation.metrics %s need the reference's decoding to instances: not computed here",
-                           [n for n in names if n in INSTANCE_METRICS])
+        # with a decoding step the instance metrics are computed below, from the segmentation where it lies; `nerl` never is
+        from .metrics import INSTANCE_METRIC_NAMES
+        skipped = [n for n in names if n in INSTANCE_METRICS and (decode_plan is None or n not in INSTANCE_METRIC_NAMES)]
+        instance_names = [n for n in names if n in INSTANCE_METRIC_NAMES] if decode_plan is not None else []
+        if skipped:
+            logger.warning("evaluation.metrics %s need the reference's decoding to instances: not computed here", skipped)
         # channel 0 of the prediction where it lies (device: the HIP count kernel; the chunked path's host array: torch on the CPU)
         metrics.update(voxel_metrics(pred_t[0, 0], torch.from_numpy(lab), names or None,
                                      float(getattr(ev, "prediction_threshold", 0.5)) if ev is not None else 0.5))
@@ -274,7 +280,8 @@ def run_test(cfg, args) -> dict:
         # once, as int32, and are stored in the reference's compact dtype
         from .utils.h5lite import get_h5_backend
         t1 = time.perf_counter()
-        seg = compact_labels(run_decoding(cfg, pred_t[0].to(dev)).cpu().numpy())
+        labels_dev = run_decoding(cfg, pred_t[0].to(dev))
+        seg = compact_labels(labels_dev.cpu().numpy())
         metrics["instances"] = int(seg.max()) if seg.size else 0
         metrics["decode_seconds"] = time.perf_counter() - t1
         be = get_h5_backend()
@@ -282,6 +289,22 @@ def run_test(cfg, args) -> dict:
             raise RuntimeError("writing the segmentation needs h5py or the in-repo libpytc_h5.so (built from csrc/host/h5io.c against libhdf5)")
         with be.File(out_dir / f"{name}_segmentation.h5", "w") as fh:
             fh.create_dataset("main", data=seg)
+        if instance_names:
+            # evaluation.metrics: adapted Rand, VOI and instance accuracy from ONE label-pair table (csrc/pair_table_kernels.hip), built from
+            # the int32 labels the decoder left on the device and the label volume uploaded as integers (a float file through
+            # .astype(int64), the reference's .long()).  What comes back is the table's 16-cell record and the pairs over the threshold.
+            t2 = time.perf_counter()
+            from .metrics import instance_metrics
+            if seg.size and seg.flat[0] == 0:
+                labels_dev.view(-1)[0] = 0                   # compact_labels' background quirk: the metrics are those of the stored ids
+            lab_ids = torch.from_numpy(np.ascontiguousarray(lab.astype(np.int64) if lab.dtype.kind == "f" else lab)).to(dev).squeeze()
+            seg_ids = labels_dev.squeeze()
+            if tuple(seg_ids.shape) != tuple(lab_ids.shape):
+                logger.warning("Cannot compute metrics: incompatible shapes after alignment, pred=%s, labels=%s", tuple(seg_ids.shape),
+                               tuple(lab_ids.shape))
+            else:
+                metrics.update(instance_metrics(seg_ids, lab_ids, instance_names, float(getattr(ev, "instance_iou_threshold", 0.5))))
+                metrics["instance_metrics_seconds"] = time.perf_counter() - t2
     (out_dir / f"{name}_metrics.json").write_text(json.dumps(metrics, indent=2))
     logger.info("test done: %s", metrics)
     return metrics

@@ -12,8 +12,9 @@ The formulas are the published definitions of the torchmetrics classes the refer
       jaccard = TP / (TP + FP + FN), dice = 2 TP / (2 TP + FP + FN), accuracy = (TP + TN) / total, each 0 when its denominator is 0;
   multi-class: TP_k = c[k][k], FP_k = column sum - TP_k, FN_k = row sum - TP_k; jaccard and dice are the mean of the binary formulas
       over the classes with TP_k + FP_k + FN_k > 0 (macro; 0 when no class is present), accuracy = sum_k TP_k / total (micro).
-Instance-level names (adapted_rand, voi, instance_accuracy...) need a decoded segmentation, which stays with the reference; any name
-outside {jaccard, dice, accuracy} is ignored here, as the reference ignores it in validation.
+Instance-level names (adapted_rand, voi, instance_accuracy, instance_accuracy_detail) need a decoded segmentation: test mode computes
+them after its decoding step from a label-pair table on the device (`pytorch_connectomics_amd/metrics/`); any
+name outside {jaccard, dice, accuracy} is ignored here, as the reference ignores it in validation.
 """
 from __future__ import annotations
 
