@@ -41,8 +41,10 @@ extern "C" {
  * dtype code only that entry takes.
  * 15: pytc_pair_table_runs / _build / _matches (the sparse contingency table of two id volumes and the integer record adapted Rand, VOI
  * and instance matching are functions of) with their host queries, and pytc_pair_hash.
+ * 16: pytc_label_cc and pytc_label_cc_dust (connected components of int32 id volumes at connectivity 6 / 18 / 26, batched, and the
+ * size filter over their numbering) with their host queries.
  * Bumped whenever a struct layout or the meaning of an argument changes; _native.py refuses a library of another version. */
-#define PYTC_ABI_VERSION 15
+#define PYTC_ABI_VERSION 16
 
 #define PYTC_OK 0
 #define PYTC_ERR_INVALID 1     /* bad argument (shape, dtype, alignment) */
@@ -1188,6 +1190,39 @@ int pytc_affinity_cc_tile(int axis);
 int64_t pytc_affinity_cc_blocks(int64_t voxels);
 int pytc_affinity_cc(const void* c0, const void* c1, const void* c2, int dtype, float threshold, int edge_offset, void* edges, void* parent,
                      int32_t* counts, int32_t* labels, int32_t* count, int A0, int A1, int A2, void* stream);
+
+/* Connected components of int32 id volumes (cc3d.connected_components as data/processing/transforms.py:537-581 and decoding/stage.py:
+ * 87-111 call it) and the size filter of cc3d.dust over their numbering.  Integers only.
+ *   ids          N contiguous (A0, A1, A2) volumes of int32, one after the other.  Two voxels of one sample are joined iff they carry
+ *                the same id, the id is not 0, and they are neighbours under `connectivity`.  Every non-zero value is an id, negative
+ *                ones included.  Components never cross a sample.
+ *   connectivity 6 (faces: 3 forward offsets), 18 (and face diagonals: 9) or 26 (and corners: 13); another one returns
+ *                PYTC_ERR_UNSUPPORTED
+ *   flags        N A0 A1 A2 bytes of scratch     parent  N A0 A1 A2 uint32 of scratch
+ *   counts       pytc_label_cc_counts(N, A0 A1 A2) int32 of scratch
+ *   labels       int32, the shape of ids: 0 where the id is 0, else 1 .. K_n in raster order of every component's smallest voxel,
+ *                anew in every sample          count  N int32: K_n
+ * N A0 A1 A2 < 2^31 - 1 (PYTC_ERR_UNSUPPORTED at or above it).  No buffer may overlap another (PYTC_ERR_INVALID).  Eight launches on
+ * `stream` for any N (csrc/label_cc_kernels.hip): union-find in LDS per 8 x 8 x 32 tile from the staged ids, agent-scope atomicMin for
+ * every forward offset that leaves a tile -- through a face, an edge or a corner -- and the flatten / rank / scan / number launches of
+ * pytc_affinity_cc over the batch, then the per-sample bases.  No launch waits for another workgroup, nothing is read back, nothing
+ * synchronises with the host.
+ * pytc_label_cc_dust, over labels and count as pytc_label_cc left them: out[v] = 0 where the component of v has fewer than min_size
+ * voxels (strict), else labels[v]; survivors keep their numbers.  kept[n] = the components of sample n that stay.  min_size >= 1
+ * (the caller skips the call otherwise).
+ *   table        pytc_label_cc_table(N, A0 A1 A2) int32 of scratch, cell n V + label - 1; the `parent` of pytc_label_cc is that large
+ *                and is free once that call's launches are enqueued ahead on the same stream
+ *   out          int32, the shape of labels; may BE labels (in place), may not overlap it otherwise          kept  N int32
+ * Four launches: the cells in use are cleared, sizes are counted with integer atomics, the survivors are counted, the filter is applied.
+ * Host queries: the tile extent along axis 0 / 1 / 2, the voxels of a rank block, the entries of counts and of table (0: out of range). */
+int pytc_label_cc_tile(int axis);
+int64_t pytc_label_cc_rank_block(void);
+int64_t pytc_label_cc_counts(int64_t samples, int64_t voxels);
+int64_t pytc_label_cc_table(int64_t samples, int64_t voxels);
+int pytc_label_cc(const int32_t* ids, int connectivity, void* flags, void* parent, int32_t* counts, int32_t* labels, int32_t* count, int N,
+                  int A0, int A1, int A2, void* stream);
+int pytc_label_cc_dust(const int32_t* labels, const int32_t* count, int min_size, int32_t* table, int32_t* out, int32_t* kept, int N,
+                       int A0, int A1, int A2, void* stream);
 
 /* The label-pair table of two id volumes (metrics/segmentation_numpy.py adapted_rand, voi, instance_matching, instance_matching_simple):
  * n[g][s] = the voxels with ground-truth id g and segmentation id s, as an open-addressing hash table, and the integer record those

@@ -91,5 +91,55 @@ PYTC_CC_HD bool may_be_head(const uint8_t* edges, long v, const long (&unit)[3])
   return true;
 }
 
+// ---- id volumes (label_cc_kernels.hip): voxels are joined iff they carry the same non-zero id and are 6-, 18- or 26-neighbours.
+// The neighbourhood a voxel looks at is the 17 offsets (d0, d1, d2) with d0 in {0, 1} and d1, d2 in {-1, 0, 1}, bit
+// (d0 3 + d1 + 1) 3 + d2 + 1 of a mask; bit 4 is the voxel itself.  Bits 5 .. 17 are the 13 FORWARD offsets, the ones that lead to a
+// larger index: every edge of the graph is the forward offset of exactly one of its two ends.  `level` is the largest number of
+// non-zero components an offset may have: 1, 2, 3 for connectivity 6, 18, 26.
+constexpr int NB_SELF = 4, NB_BITS = 18;
+
+PYTC_CC_HD int connectivity_level(int connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0; }
+
+PYTC_CC_HD int nb_bit(int d0, int d1, int d2) { return (d0 * 3 + d1 + 1) * 3 + d2 + 1; }
+
+PYTC_CC_HD void nb_offset(int b, int& d0, int& d1, int& d2) {
+  d0 = b / 9;
+  d1 = (b / 3) % 3 - 1;
+  d2 = b % 3 - 1;
+}
+
+// Offset b is one a voxel has to compare its id with: a forward offset within the level, and with diagonals (level > 1) the backward
+// offsets of its own plane too, which lie between the voxel and a forward diagonal neighbour.
+PYTC_CC_HD bool nb_wanted(int b, int level) {
+  int d0, d1, d2;
+  nb_offset(b, d0, d1, d2);
+  const int nz = d0 + (d1 != 0) + (d2 != 0);
+  return b != NB_SELF && nz <= level && (b > NB_SELF || level > 1);
+}
+
+// same: bit b set iff the voxel at offset b lies inside and carries the id of this voxel, for every wanted b.  -> the forward edges
+// this voxel has to unite.  A diagonal edge v -- w is left out when a voxel m between them (every component of its offset is that of
+// w or 0) carries the id too: v -- m and m -- w have fewer non-zero components each, are edges of the same graph, and are kept or
+// left out by the same rule, which ends at the face edges: those are never left out.  The components are the same; the inside of a
+// solid segment unites three face edges per voxel at any connectivity.
+PYTC_CC_HD uint32_t needed_edges(uint32_t same, int level) {
+  uint32_t out = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int b = NB_SELF + 1; b < NB_BITS; ++b) {
+    int d0, d1, d2;
+    nb_offset(b, d0, d1, d2);
+    const int nz = d0 + (d1 != 0) + (d2 != 0);
+    uint32_t between = 0;
+    for (int s = 1; s < 7; ++s) {
+      const int mb = nb_bit((s & 4) ? d0 : 0, (s & 2) ? d1 : 0, (s & 1) ? d2 : 0);
+      if (mb != b && mb != NB_SELF) between |= 1u << mb;
+    }
+    if (nz <= level && ((same >> b) & 1u) && !(same & between)) out |= 1u << b;
+  }
+  return out;
+}
+
 }  // namespace cc
 }  // namespace pytc

@@ -41,6 +41,7 @@ _ALLOWED = {
     "instance_boundary": {"thickness", "edge_mode", "mode"},
     "polarity": {"exclusive"},
 }
+RELABEL_CONNECTIVITIES = (6, 18, 26)
 Half = Tuple[int, int, int]
 Chain = Tuple[Half, ...]             # the erosions a source buffer went through, in order; () is the patch itself
 
@@ -91,7 +92,15 @@ class LabelTargetTransform:
     """The planned stacked layout and the device call.  `.channels` = C, `.channel_names`, `.uses_mask`, `.sources` (the erosion chains
     the channels read), `.table` (the kernel's channel rows)."""
 
-    def __init__(self, tasks: Sequence[Any], *, erosion: int = 0, stack_outputs: bool = True, output_dtype: Any = "float32"):
+    def __init__(self, tasks: Sequence[Any], *, erosion: int = 0, stack_outputs: bool = True, output_dtype: Any = "float32",
+                 relabel_connected_components: bool = False, relabel_connectivity: int = 6):
+        # RelabelConnectedComponentsd (build.py:102-111): the pieces of an id that the crop disconnected become instances of their own,
+        # before the augmentations, the erosion and the targets (`relabel`, applied by `relabelled_batches`)
+        self.relabel_connected_components = bool(relabel_connected_components)
+        if isinstance(relabel_connectivity, bool) or int(relabel_connectivity) != relabel_connectivity or \
+                int(relabel_connectivity) not in RELABEL_CONNECTIVITIES:
+            raise ValueError(f"label_transform.relabel_connectivity must be one of {RELABEL_CONNECTIVITIES}, got {relabel_connectivity!r}")
+        self.relabel_connectivity = int(relabel_connectivity)
         if not bool(stack_outputs):
             raise NotImplementedError("label_transform.stack_outputs: false (one key per target) is not built: the device transform "
                                       "writes the stacked tensor")
@@ -210,18 +219,40 @@ class LabelTargetTransform:
 
     @classmethod
     def from_config(cls, label_cfg: Any) -> "LabelTargetTransform":
-        """`cfg.data.label_transform` (a mapping or a namespace): targets, erosion, stack_outputs, output_dtype."""
+        """`cfg.data.label_transform` (a mapping or a namespace): targets, erosion, stack_outputs, output_dtype,
+        relabel_connected_components, relabel_connectivity."""
         targets = _get(label_cfg, "targets", None)
         if targets is None:
             targets = []
         tasks = [targets] if isinstance(targets, str) or hasattr(targets, "items") else list(targets)
         return cls(tasks, erosion=int(_get(label_cfg, "erosion", 0) or 0), stack_outputs=_get(label_cfg, "stack_outputs", True),
-                   output_dtype=_get(label_cfg, "output_dtype", "float32"))
+                   output_dtype=_get(label_cfg, "output_dtype", "float32"),
+                   relabel_connected_components=bool(_get(label_cfg, "relabel_connected_components", False) or False),
+                   relabel_connectivity=_none_as(_get(label_cfg, "relabel_connectivity", 6), 6))
 
     def describe(self) -> List[Dict[str, Any]]:
         """One plain row per channel: name, kind, source chain, flags, values (what the tests and the numpy model read)."""
         return [{"name": n, "kind": kind, "chain": chain, "flags": flags, "v": list(v)}
                 for n, (kind, chain, flags, v) in zip(self.channel_names, self._rows)]
+
+    def relabel(self, label: torch.Tensor) -> torch.Tensor:
+        """The id patch with every connected piece of an id numbered on its own (hip_ops.label_cc per sample, every non-zero id a
+        label, -1 among them), then -1 written back where the patch was -1 (transforms.py:573-579).  label: integer ids (B, D, H, W) or
+        (B, 1, D, H, W) on the device; the shape is kept.  With the key off this is the identity: `label` itself, no launch."""
+        if not self.relabel_connected_components:
+            return label
+        from .. import hip_ops as ops
+        if not isinstance(label, torch.Tensor):
+            raise TypeError(f"label must be a tensor, got {type(label).__name__}")
+        ids = label[:, 0] if label.dim() == 5 and label.shape[1] == 1 else label
+        if ids.dim() != 4:
+            raise ValueError(f"label must be (B, D, H, W) or (B, 1, D, H, W) instance ids, got {tuple(label.shape)}")
+        ids = labels_to_int32(ids)
+        if not ids.is_cuda:
+            raise RuntimeError("label must be a CUDA(HIP) tensor: pytorch_connectomics_amd has no CPU path")
+        out, _count, _kept = ops.label_cc(ids, self.relabel_connectivity)
+        out.masked_fill_(ids == -1, -1)
+        return out.reshape(label.shape)
 
     def __call__(self, label: torch.Tensor, *, mask_dtype: torch.dtype = torch.bool) -> Dict[str, torch.Tensor]:
         from .. import hip_ops as ops
@@ -243,6 +274,21 @@ class LabelTargetTransform:
         if mask is not None:
             out["label_mask"] = mask
         return out
+
+
+def _none_as(value, default):
+    return default if value is None else value
+
+
+def relabelled_batches(batches: Iterable[Dict[str, torch.Tensor]], transform: LabelTargetTransform,
+                       device) -> Iterator[Dict[str, torch.Tensor]]:
+    """Wrap a batch iterator whose "label" holds instance ids: every tensor moves to `device` and the label goes through
+    `transform.relabel`.  The seam of the reference (build.py:307-316): after the crop, before the augmentations.  The caller wraps
+    nothing when the key is off."""
+    for batch in batches:
+        out = {k: (v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}
+        out["label"] = transform.relabel(out["label"])
+        yield out
 
 
 def device_target_batches(batches: Iterable[Dict[str, torch.Tensor]], transform: LabelTargetTransform, device,

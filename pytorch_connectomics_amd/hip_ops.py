@@ -2893,6 +2893,56 @@ def affinity_cc(aff: torch.Tensor, threshold: float, edge_offset: int = 0, chann
     return labels, count
 
 
+# ------------------------------------------------------------------ components of id volumes (csrc/label_cc_kernels.hip)
+LABEL_CC_CONNECTIVITIES = (6, 18, 26)
+
+
+def label_cc(ids: torch.Tensor, connectivity: int = 6, min_size: int = 0):
+    """Connected components of an id volume (D, H, W) or a batch of them (N, D, H, W), int32 or int64 on the device (include/pytc_hip.h
+    pytc_label_cc, pytc_label_cc_dust): voxels are joined iff they carry the same non-zero id and are 6-, 18- or 26-neighbours; every
+    non-zero value is an id, negative ones included; components never cross a sample.
+    -> (labels int32, the shape of `ids`: 0 where the id is 0, else 1 .. K in raster order of every component's first voxel, anew in
+    every sample; count int32[N] = K per sample; kept int32[N] = the components that stay).  With min_size > 0 a component of fewer
+    than min_size voxels becomes 0 and the others keep their numbers (gaps remain); with min_size <= 0 nothing is removed and `kept`
+    is `count`.  Everything stays on the device, on the current stream, nothing synchronised -- except the range check of int64 ids."""
+    _on_device(ids, "ids")
+    if ids.dim() not in (3, 4) or ids.numel() == 0 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"ids must be a non-empty (D, H, W) or (N, D, H, W) tensor of int32 / int64, got {ids.dtype} {tuple(ids.shape)}")
+    if isinstance(connectivity, bool) or int(connectivity) != connectivity or int(connectivity) not in LABEL_CC_CONNECTIVITIES:
+        raise ValueError(f"connectivity must be one of {LABEL_CC_CONNECTIVITIES}, got {connectivity!r}")
+    if isinstance(min_size, bool) or int(min_size) != min_size or int(min_size) > 2 ** 31 - 1:
+        raise ValueError(f"min_size must be an integer below 2^31, got {min_size!r}")
+    N = int(ids.shape[0]) if ids.dim() == 4 else 1
+    A0, A1, A2 = (int(v) for v in ids.shape[-3:])
+    V = A0 * A1 * A2
+    if N * V >= 2 ** 31 - 1:
+        raise NotImplementedError(f"ids of {N} x {V} voxels: indices and component numbers are 31 bits (2^31 - 1 voxels or more are not built)")
+    if ids.dtype == torch.int64:
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < -(2 ** 31) or hi > 2 ** 31 - 1:
+            raise ValueError(f"ids span [{lo}, {hi}]: outside int32, which the component kernels read")
+        ids = ids.to(torch.int32)
+    ids = ids.contiguous()
+    dev = ids.device
+    lib = nat.lib()
+    flags = torch.empty(N * V, dtype=torch.uint8, device=dev)
+    parent = torch.empty(int(lib.pytc_label_cc_table(N, V)), dtype=torch.int32, device=dev)
+    counts = torch.empty(int(lib.pytc_label_cc_counts(N, V)), dtype=torch.int32, device=dev)
+    labels = torch.empty(ids.shape, dtype=torch.int32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    # algorithmic bytes: the ids read by local and by merge's boundary voxels, parent written by local, read and written by flatten
+    # and rank, read by apply, the flag byte written and read, the labels written
+    _run(f"label_cc[{int(connectivity)}]", N * V * (2 * 4 + 6 * 4 + 3 + 4), lib.pytc_label_cc, _p(ids), int(connectivity), _p(flags),
+         _p(parent), _p(counts), _p(labels), _p(count), N, A0, A1, A2, _stream(), symbol="label_cc")
+    if int(min_size) <= 0:
+        return labels, count, count
+    kept = torch.empty(N, dtype=torch.int32, device=dev)
+    # the size table is the parent array: every launch that reads it as parents is ahead on the stream; the filter runs in place
+    _run("label_cc_dust", N * V * (4 + 4 + 4 + 4), lib.pytc_label_cc_dust, _p(labels), _p(count), int(min_size), _p(parent), _p(labels),
+         _p(kept), N, A0, A1, A2, _stream(), symbol="label_cc_dust")
+    return labels, count, kept
+
+
 # ------------------------------------------------------------------ label-pair table (csrc/pair_table_kernels.hip)
 PAIR_RECORD_CELLS = ("N", "N1", "S_A", "S_B", "S_AB", "c", "n_true", "n_pred", "pairs", "global_updates", "x_n", "x_a", "x_b", "lost",
                      "voi_split_fixed", "voi_merge_fixed")

@@ -174,6 +174,10 @@ def run_test(cfg, args) -> dict:
     dev = torch.device("cuda", 0)
     from .decoding import compact_labels, plan_decoding, run_decoding
     decode_plan = plan_decoding(cfg)                          # a decoding step this engine does not build fails here, before the inference
+    post_plan = None
+    if decode_plan is not None:
+        from .decoding.postprocess import plan_postprocessing, run_postprocessing
+        post_plan = plan_postprocessing(cfg)                  # and so does a postprocessing block it does not build
     torch.manual_seed(int(cfg.system.seed))
     model = build_model(cfg).to(dev).eval()
     if args.checkpoint:
@@ -281,9 +285,29 @@ def run_test(cfg, args) -> dict:
         from .utils.h5lite import get_h5_backend
         t1 = time.perf_counter()
         labels_dev = run_decoding(cfg, pred_t[0].to(dev))
+        kept, post_seconds = None, 0.0
+        if post_plan is not None:
+            # decoding.postprocessing (stage.py:43-124, applied at :284): between the decode step and what is saved and scored.
+            # postprocess_seconds is the device work alone, synchronised on both sides; decode_seconds keeps its meaning (the decode
+            # step, the copy to the host and the compact dtype) and leaves the postprocessing out
+            before = int(labels_dev.max()) if labels_dev.numel() else 0      # K of the decode step (waits for it)
+            t_post = time.perf_counter()
+            labels_dev, _count, kept = run_postprocessing(post_plan, labels_dev)
+            labels_dev = labels_dev.contiguous()
+            torch.cuda.synchronize()
+            post_seconds = time.perf_counter() - t_post
         seg = compact_labels(labels_dev.cpu().numpy())
         metrics["instances"] = int(seg.max()) if seg.size else 0
-        metrics["decode_seconds"] = time.perf_counter() - t1
+        metrics["decode_seconds"] = time.perf_counter() - t1 - post_seconds
+        if post_plan is not None:
+            if kept is not None:
+                # the surviving components: ids keep their gaps, so the largest id no longer counts them.  compact_labels zeroes voxel
+                # 0 of a volume without background: a component that was that voxel alone is gone from the stored ids
+                first = int(labels_dev.view(-1)[0]) if labels_dev.numel() else 0
+                lost = first != 0 and seg.flat[0] == 0 and int((labels_dev == first).sum()) == 1
+                metrics["instances"] = int(kept[0]) - (1 if lost else 0)
+            metrics["postprocess_seconds"] = post_seconds
+            metrics["instances_before_postprocess"] = before
         be = get_h5_backend()
         if be is None:
             raise RuntimeError("writing the segmentation needs h5py or the in-repo libpytc_h5.so (built from csrc/host/h5io.c against libhdf5)")
@@ -355,6 +379,13 @@ def train_batches(cfg, module, dev, *, rank: int = 0, demo: bool = False):
         if tuple(lab.shape) != tuple(vol.shape):
             raise ValueError(f"data.train.label {tuple(lab.shape)} and data.train.image {tuple(vol.shape)} differ in shape")
     else:
+        lt = getattr(cfg.data, "label_transform", None)
+        if lt is not None and bool(getattr(lt, "relabel_connected_components", False) or False):
+            # the relabel acts on the id patch the device targets are built from; without targets the label is read as a float
+            # foreground / class volume and no id patch exists: said, not ignored
+            raise NotImplementedError("data.label_transform.relabel_connected_components: true needs data.label_transform.targets: "
+                                      "the relabel is a step of the device target transform, and without targets the label volume is "
+                                      "fed as foreground / class numbers, not as instance ids")
         lab = torch.from_numpy(np.ascontiguousarray(read_volume(str(cfg.data.train.label))).astype(np.float32))
     # a class-index term (CrossEntropyLoss, or to_onehot_y of the softmax losses) reads the label volume's class numbers; every
     # other configuration keeps the binary foreground target
@@ -377,7 +408,13 @@ def train_batches(cfg, module, dev, *, rank: int = 0, demo: bool = False):
             yield {"image": torch.stack(xs), "label": torch.stack(ys)}
     # the reference's seam (data/augmentation/build.py:309-334): after the crop and the normalisation, before the label erosion and the
     # targets.  A plan with nothing to do wraps nothing: the same batches, no launch, no draw
-    source = augmented_batches(sampler(), augment, dev) if augment.enabled else sampler()
+    source = sampler()
+    if plan is not None and plan.relabel_connected_components:
+        # data.label_transform.relabel_connected_components (build.py:102-111, :307): pieces of an id the crop disconnected become
+        # instances of their own, before the augmentations see the patch
+        from .data import relabelled_batches
+        source = relabelled_batches(source, plan, dev)
+    source = augmented_batches(source, augment, dev) if augment.enabled else source
     if plan is None:
         return source
     batches = device_target_batches(source, plan, dev, mask_dtype=torch.float32)
