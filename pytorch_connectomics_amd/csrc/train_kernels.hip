@@ -2066,11 +2066,12 @@ static int dw_wgrad_impl(const void* g, const void* x, float* dW, float* db, flo
   const long nW = (long)K * K * K * C;
   float* dWp = workspace;
   float* dbp = workspace + (long)total_slots * nW;
+  float* dbq = db ? dbp : nullptr;                 // no bias wanted: no bias partials written (as the march and vector forms)
   hipStream_t s = (hipStream_t)stream;
   PYTC_DISPATCH_DTYPE(dtype, "dw_wgrad", T,
     constexpr int V8 = elems_per_16b_of<T> / 2;      // make_wg's widest
-    if (int rc = vec == V8 ? launch_dwwg<T, V8>(g, x, dWp, dbp, q, s) : vec == 2 ? launch_dwwg<T, 2>(g, x, dWp, dbp, q, s)
-                                                                                  : launch_dwwg<T, 1>(g, x, dWp, dbp, q, s))
+    if (int rc = vec == V8 ? launch_dwwg<T, V8>(g, x, dWp, dbq, q, s) : vec == 2 ? launch_dwwg<T, 2>(g, x, dWp, dbq, q, s)
+                                                                                  : launch_dwwg<T, 1>(g, x, dWp, dbq, q, s))
       return rc);
   if (slots_out) *slots_out = total_slots;
   if (reduce) reduce_slots_pair(dWp, dW, nW, dbp, db, (long)C, total_slots, s);
